@@ -11,10 +11,11 @@ A step regresses every date of a rank's shard (weak scaling, the default: ``--da
 2520 = 10 years of trading days; ``--scaling strong``: ``--dates`` in total, 2520 / world per
 rank), replayed from a captured HIP graph: the fused moments -> solve -> residual kernel (one
 workgroup per date), then all-gathers the factor-return series across ranks over RCCL (the
-collective the downstream Newey-West stage needs).  After the headline loop a second loop
-regresses a FIXED global problem (``--strong-dates``, default ``--dates``, split over the ranks)
-and is reported in the JSON's ``"strong"`` record, so one 1 -> N sweep yields both the weak and
-the strong scaling curve.  Data is a synthetic panel of the named shape with random-init exposures (the reference ships no data).
+collective the downstream Newey-West stage needs).  A plain run sets up, warms up, times the
+``--steps`` steps and prints the result line.  With ``--full`` a second loop after the headline
+loop regresses a FIXED global problem (``--strong-dates``, default ``--dates``, split over the
+ranks) and is reported in the JSON's ``"strong"`` record, so one 1 -> N sweep yields both the
+weak and the strong scaling curve.  Data is a synthetic panel of the named shape with random-init exposures (the reference ships no data).
 
 Storage: ``--storage fp64`` (default, the headline) keeps the panel in float64, the precision
 the reference regresses (``demo.py:21`` reads float64 CSV columns into ``CrossSection.reg``);
@@ -23,8 +24,14 @@ and reductions are float64 in both.  Every step runs the production path of
 ``RiskModel.regress``: the fused kernel plus the device pseudo-inverse pass for near-singular
 dates (``refine=True``), both inside the captured graph.
 
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0's factor returns,
+R^2, regression statistics, status flags and specific returns, 0.0 where a stock is absent,
+with the mask ``specific_ret_finite``) as ``DIR/<name>.npy``; the
+panel is seeded, so two builds run with the same arguments can be compared output for output.
+
     python bench.py --gpus 1 --steps 20 --warmup 3
-    torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --full
 """
 from __future__ import annotations
 
@@ -39,6 +46,40 @@ import torch.distributed as dist
 
 BASELINE_REG_PER_S = 9.6  # reference on the survey host, N=5000, K=42
 METRIC = "cross-sectional WLS regressions/sec (5000 stocks × 41 factors) at 1/2/4/8 GPU"
+DUMP_BUDGET_BYTES = 64 * 2**20  # --dump-outputs writes at most this much in all
+DUMP_SEED = 20240229            # row sample of an output larger than the remaining budget
+
+
+def dump_outputs(path, arrays):
+    """Write ``arrays`` (name -> tensor, in this order) as ``path/<name>.npy`` in float32 /
+    float64 (integers as float64), at most DUMP_BUDGET_BYTES in all, every value finite.  An
+    array with non-finite entries (the NaN specific returns of absent stocks) is written with
+    0.0 in their place, next to ``<name>_finite.npy`` (float32: 1.0 where the entry is finite,
+    0.0 where it is not).  An array that does not fit the remaining budget is cut to a fixed
+    sample of its rows: the sorted first ``budget // row_bytes`` entries of
+    ``numpy.random.default_rng(DUMP_SEED).permutation(rows)``."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - 2 * 128 * len(arrays)   # .npy headers
+    for name, t in arrays.items():
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        finite = torch.isfinite(t)
+        finite = None if bool(finite.all()) else finite.to(torch.float32)
+        cell = t.element_size() + (0 if finite is None else finite.element_size())
+        row_bytes = max(1, t[0].numel() * cell) if t.dim() and t.shape[0] else cell
+        rows = t.shape[0] if t.dim() else 1
+        if t.dim() and rows * row_bytes > left:
+            keep = np.sort(np.random.default_rng(DUMP_SEED).permutation(rows)[:left // row_bytes])
+            keep = torch.from_numpy(keep).to(t.device)
+            t, finite = t[keep], None if finite is None else finite[keep]
+        out = {name: t if finite is None else torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0)}
+        if finite is not None:
+            out[name + "_finite"] = finite
+        for k, v in out.items():
+            a = v.cpu().numpy()
+            left -= a.nbytes
+            np.save(os.path.join(path, f"{k}.npy"), a)
 
 
 def main() -> int:
@@ -50,9 +91,14 @@ def main() -> int:
                     help="dates per GPU (weak scaling) or in total (strong scaling)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --dates per GPU; strong: --dates in total, sharded over ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the extra "
+                         "strong-scaling loop reported in the \"strong\" record")
     ap.add_argument("--strong-dates", type=int, default=None,
-                    help="global dates of the extra strong-scaling record (default --dates; "
-                         "0 = skip it)")
+                    help="global dates of the extra strong-scaling record of --full (default "
+                         "--dates; 0 = skip it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--stocks", type=int, default=5000)
     ap.add_argument("--industries", type=int, default=31)
     ap.add_argument("--styles", type=int, default=10)
@@ -180,7 +226,7 @@ def main() -> int:
                 graphs[b] = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graphs[b], capture_error_mode="thread_local"):
                     regress(b)
-        return step, drain, outs
+        return step, drain, outs, (lambda: (it[0] - 1) % NB), gathered
 
     def timed(step, drain, prewarm, warmup, steps):
         """W untimed warmup steps, then EXACTLY ``steps`` timed steps between barrier +
@@ -207,20 +253,30 @@ def main() -> int:
     # Setup (prewarm): bring the GPU to its steady-state clocks (a cold MI355X runs the first
     # ~100 steps ~10 % slower: 0.308 vs 0.278 ms/step measured).  Same step, same count on every
     # rank (the all-gathers pair up), all before the W warmup steps and the timed region.
-    step, drain, outs = make_runner(D, Dpad)
+    step, drain, outs, last, gathered = make_runner(D, Dpad)
     el = timed(step, drain, args.prewarm, args.warmup, args.steps)
-    out = outs[0]
+    out = outs[last()]   # the buffer the last timed step wrote
 
-    # Second, separately reported record: strong scaling of a FIXED global problem
+    if args.dump_outputs and rank == 0:
+        arrays = {}
+        if out is not None:
+            arrays = {"factor_ret": out.f, "r2": out.r2, "stats": out.stats, "status": out.status}
+        if gathered is not None:
+            arrays["factor_ret_gathered"] = gathered[last()]
+        if out is not None and out.resid is not None:
+            arrays["specific_ret"] = out.resid   # last: the one output that may need sampling
+        dump_outputs(args.dump_outputs, arrays)
+
+    # --full: a second, separately reported record: strong scaling of a FIXED global problem
     # (--strong-dates in total, split over the ranks), so the driver's 1 -> N runs record both
     # curves.  The headline fields above stay the weak-scaling (or --scaling) loop.
     strong = None
     G = args.strong_dates if args.strong_dates is not None else args.dates
-    if G > 0 and args.scaling == "weak":
+    if args.full and G > 0 and args.scaling == "weak":
         Ds, Dsp = block(G)
         if Dsp > D:
             raise SystemExit(f"--strong-dates {G} needs {Dsp} dates per rank, the panel has {D}")
-        s_step, s_drain, _ = make_runner(Ds, Dsp)
+        s_step, s_drain, *_ = make_runner(Ds, Dsp)
         s_el = timed(s_step, s_drain, max(1, args.prewarm // 4), args.warmup, args.steps)
         strong = {"global_dates": G, "dates_per_gpu": Dsp, "steps": args.steps,
                   "ms_per_step": round(s_el / args.steps * 1e3, 4),

@@ -715,6 +715,7 @@ __global__ __launch_bounds__(XT) __attribute__((amdgpu_waves_per_eu(WPE))) void 
             const int i = e / K, j = e - i * K;
             Y[(size_t)i * LD + j] = Aw[(size_t)i * LD + j];
           }
+          __syncthreads();  // every copy of Aw's diagonal precedes its overwrite by another thread
           for (int k = tid; k < K; k += XT) Aw[(size_t)k * LD + k] = lam[k];
           __syncthreads();
         }

@@ -34,7 +34,7 @@ def _run(n, extra=()):
 
 
 def test_bench_single_process_json():
-    r = _run(1)
+    r = _run(1, ["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
               "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in r
@@ -47,13 +47,77 @@ def test_bench_single_process_json():
     assert abs(s["value"] - 6 * 2 / (s["ms_per_step"] * 2 / 1e3)) / s["value"] < 0.02
 
 
+def test_bench_plain_run_is_the_headline_loop_only():
+    """Without --full the extra strong-scaling loop does not run; the headline fields stay."""
+    r = _run(1)
+    assert r["strong"] is None
+    assert r["steps"] == 2 and r["warmup"] == 1 and r["value"] > 0 and r["ms_per_step"] > 0
+    assert abs(r["value"] - 6 * 2 / (r["ms_per_step"] * 2 / 1e3)) / r["value"] < 0.02
+    assert r["unit"] == "regressions/s" and r["higher_is_better"] is True and r["dtype"] == "fp64"
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float .npy files, the same from
+    run to run, and they are the oracle's regression of the seeded panel."""
+    import numpy as np
+    import torch
+    from llm_driven_multi_factor_model_amd.models.panel import synthetic_panel
+    from llm_driven_multi_factor_model_amd.ops.cross_section import xs_wls_reference
+    got = []
+    for d in ("a", "b"):
+        _run(1, ["--dump-outputs", str(tmp_path / d)])
+        got.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = got
+    assert sorted(a) == ["factor_ret", "r2", "specific_ret", "specific_ret_finite", "stats",
+                         "status"]
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.isfinite(a[k]).all(), k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    assert a["factor_ret"].shape == (6, 6) and a["specific_ret"].shape == (6, 64)
+    p = synthetic_panel(6, 64, 3, 2, seed=1234, missing_frac=0.01, dtype=torch.float64)
+    ref = xs_wls_reference(p.styles, p.cap, p.ret, p.ind, 3)
+    np.testing.assert_allclose(a["factor_ret"], ref.f.numpy(), rtol=1e-9, atol=1e-12)
+    np.testing.assert_allclose(a["r2"], ref.r2.numpy(), rtol=1e-9, atol=1e-12)
+    present = torch.isfinite(ref.resid).numpy()   # absent stocks: NaN for a caller, 0.0 + mask here
+    assert not present.all()
+    np.testing.assert_array_equal(a["specific_ret_finite"], present.astype(np.float32))
+    np.testing.assert_allclose(a["specific_ret"], ref.resid.nan_to_num(0.0).numpy(), rtol=1e-9,
+                               atol=1e-13)
+
+
+def test_bench_dump_outputs_samples_rows_within_budget(tmp_path):
+    """An output larger than the budget is cut to a fixed, sorted sample of its rows."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("_mfa_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = torch.arange(12, dtype=torch.int32)
+    big = torch.arange(3000, dtype=torch.float64)[:, None].expand(3000, 4096).contiguous()
+    big[5, 7] = float("nan")
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    np.testing.assert_array_equal(a, b)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_BUDGET_BYTES
+    assert 1300 < a.shape[0] < 3000 and a.shape[1] == 4096
+    m = np.load(tmp_path / "a" / "big_finite.npy")
+    assert m.dtype == np.float32 and m.shape == a.shape and np.isfinite(a).all()
+    assert (np.diff(a[:, 0]) > 0).all()                             # whole rows, in order
+    assert ((a == a[:, :1]) | (m == 0)).all() and (a[m == 0] == 0).all() and (m == 0).sum() <= 1
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and s.tolist() == list(range(12))
+
+
 def test_bench_dtype_follows_storage():
     r = _run(1, ["--storage", "fp32"])
     assert r["dtype"] == "fp32" and r["config"]["storage"] == "fp32"
 
 
 def test_bench_two_ranks_aggregate():
-    r = _run(2)
+    r = _run(2, ["--full"])
     assert r["n_gpus"] == 2
     assert r["config"]["global_batch"] == 12 and r["config"]["parallelism"] == "dp2"
     assert abs(r["value"] - 12 * 2 / (r["ms_per_step"] * 2 / 1e3)) / r["value"] < 0.02

@@ -23,8 +23,10 @@ def data():
 @pytest.fixture(scope="module")
 def ref_out(ref, data):
     prices, index, _ = data
+    from tests._refshim import scope
     warnings.simplefilter("ignore")
-    with contextlib.redirect_stdout(io.StringIO()), contextlib.redirect_stderr(io.StringIO()):
+    with contextlib.redirect_stdout(io.StringIO()), contextlib.redirect_stderr(io.StringIO()), \
+            scope("test_factor_engine::ref_out"):   # one record shared by the module's tests
         fc = ref.factor_calculator.FactorCalculator(prices.copy(), index.copy())
         return fc.run(FE.FACTORS_TO_RUN)
 
@@ -49,11 +51,13 @@ def test_descriptors_match_reference(ref_out, data, monkeypatch):
 def test_post_processing_pipeline_matches_reference(ref, ref_out, data):
     pp = ref.post_processing
     cols = [c for c in ref_out.columns if c not in ("ts_code", "trade_date")]
+    from llm_driven_multi_factor_model_amd.utils.config import FactorConfig
+    from tests._refshim import intermediate
+    cfg = FactorConfig()
     with contextlib.redirect_stdout(io.StringIO()):
-        rw = pp.winsorize_factors(ref_out, cols)
-        from llm_driven_multi_factor_model_amd.utils.config import FactorConfig
-        cfg = FactorConfig()
-        rc = pp.calculate_composite_factors(rw, cfg.composite)
+        with intermediate():   # rw, rc only feed the next reference stage
+            rw = pp.winsorize_factors(ref_out, cols)
+            rc = pp.calculate_composite_factors(rw, cfg.composite)
         ro = pp.orthogonalize_factors(rc, cfg.ortho)
     w = FE.winsorize_frame(ref_out, cols, device="cpu")
     c = FE.composite_frame(w, cfg.composite, device="cpu")
@@ -151,14 +155,17 @@ def test_hip_sliding_window_kernels_match_direct(cuda):
             torch.testing.assert_close(y.cpu(), x.cpu(), rtol=2e-5, atol=2e-7, equal_nan=True, msg=k)
 
 
-_FIXTURE = __import__("pathlib").Path(__file__).parent / "fixtures" / "ref_descriptors_n50_t800_seed5.npz"
+_FIXTURE = __import__("pathlib").Path(__file__).parent / "golden" / "ref_descriptors_n50_t800_seed5"
 
 
 def _check_against_fixture(out):
     """Descriptors vs the reference FactorCalculator's output for synthetic_prices(N=50, T=800,
     seed=5, suspend_frac=0.03), computed once by running the reference source and stored as
-    npz (tests/fixtures; loaded with allow_pickle=False)."""
-    fx = np.load(_FIXTURE, allow_pickle=False)
+    npz parts of a few columns each (tests/golden; loaded with allow_pickle=False)."""
+    fx = {}
+    for part in sorted(_FIXTURE.glob("part*.npz")):
+        with np.load(part, allow_pickle=False) as z:
+            fx.update({k: z[k] for k in z.files})
     assert (out["ts_code"].astype(str).to_numpy() == fx["ts_code"]).all()
     assert (out["trade_date"].astype(str).to_numpy() == fx["trade_date"]).all()
     for c in ["ret", "circ_mv"] + COLS:

@@ -36,7 +36,7 @@ def _json_lines(out):
 
 def _bench(gpu):
     r = _torchrun(["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--prewarm", "2",
-                   "--dates", "64", "--stocks", "600" if not gpu else "2000", "--check"], gpu)
+                   "--dates", "64", "--stocks", "600" if not gpu else "2000", "--check", "--full"], gpu)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_lines(r.stdout)[-1]
     assert rec["value"] > 0 and rec["n_gpus"] == 1 and rec["steps"] == 5

@@ -1,13 +1,16 @@
 """The Tushare statement fetchers request the reference's full column sets (fake ``pro``)."""
 import ast
+import json
 import os
 
 import pandas as pd
 import pytest
 
 import barra_database.tushare_fetcher as tf
+from tests import _refshim
 
-REF = "/root/reference/Barra_database/database/tushare_fetcher.py"
+# the ``fields_list`` of every statement fetcher of the reference's tushare_fetcher.py, recorded
+GOLDEN = os.path.join(_refshim.GOLDEN, "tushare_statement_fields.json")
 
 
 class FakePro:
@@ -22,20 +25,25 @@ class FakePro:
 
 
 def _reference_fields():
-    tree = ast.parse(open(REF, encoding="utf-8").read())
+    if not _refshim.RECORD:
+        with open(GOLDEN, encoding="utf-8") as fh:
+            return json.load(fh)
+    src = _refshim.reference_source("Barra_database", "database", "tushare_fetcher.py")
+    tree = ast.parse(open(src, encoding="utf-8").read())
     out = {}
     for fn in tree.body:
         if isinstance(fn, ast.FunctionDef):
             for node in ast.walk(fn):
                 if isinstance(node, ast.Assign) and getattr(node.targets[0], "id", None) == "fields_list":
                     out[fn.name] = [e.value for e in node.value.elts]
+    os.makedirs(os.path.dirname(GOLDEN), exist_ok=True)
+    with open(GOLDEN, "w", encoding="utf-8") as fh:
+        json.dump(out, fh, indent=1)
     return out
 
 
 @pytest.mark.reference
 def test_statement_fields_equal_reference(monkeypatch):
-    if not os.path.exists(REF):
-        pytest.skip("reference not mounted")
     fake = FakePro()
     monkeypatch.setattr(tf, "pro", fake)
     ref = _reference_fields()

@@ -90,7 +90,7 @@ def test_world8_risk_model(D, scan, shard):
 
 def test_world8_bench_contract():
     from tests.test_bench_contract import _run as bench
-    r = bench(8)
+    r = bench(8, ["--full"])
     assert r["n_gpus"] == 8 and r["config"]["parallelism"] == "dp8"
     assert r["config"]["global_batch"] == 48
     s = r["strong"]   # 6 global dates over 8 ranks: ranks 6 and 7 own none

@@ -1,6 +1,6 @@
 """Factor sets beyond the register / LDS-resident solvers (160 < K <= 1024; VERDICT r05 Missing 2).
 
-The reference estimators work at any K (`/root/reference/Barra-master/mfm/utils.py:55-92`).  Here
+The reference estimators work at any K (`Barra-master/mfm/utils.py:55-92`).  Here
 every piece of the eigen adjustment above K = 160 runs on the XL kernels -- output-tiled MFMA draw
 covariances (`csrc/eigen.hip: mc_cov_xl_kernel`), the persistent global-slot eigen solver
 (`csrc/eigen_xl.hip`), the any-K finalize -- instead of rocSOLVER / rocBLAS behind a host sync.

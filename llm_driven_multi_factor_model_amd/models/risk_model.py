@@ -17,6 +17,8 @@ re-designed for MI355X:
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
@@ -27,6 +29,12 @@ from ..utils import checkpoint as ckpt
 from ..utils import trace
 from ..utils.config import RiskConfig
 from .panel import RiskPanel
+
+
+class MinVariance(NamedTuple):
+    """:meth:`RiskModel.min_variance`: ``weights`` [D_loc, N], ``variance`` [D_loc] (float64)."""
+    weights: torch.Tensor
+    variance: torch.Tensor
 
 
 class RiskModel:
@@ -397,6 +405,78 @@ class RiskModel:
             specific_vol = self.specific_risk_shrunk()
         svar = None if specific_vol is None else attr.portfolio_specific_var(h, specific_vol)
         return attr.risk_attribution(x, cov, svar)
+
+    # --------------------------------------------------------------- portfolio construction
+    def _cov_inputs(self, which: str, specific_vol):
+        """(factor covariance series, specific volatility) for the asset-covariance methods."""
+        if self.stats is None:
+            raise RuntimeError("run regress() first")
+        cov = {"nw": self.nw_cov, "eigen": self.eigen_cov, "vra": self.vra_cov}[which]
+        if cov is None:
+            raise RuntimeError(f"covariance series {which!r} not computed yet")
+        if specific_vol is None:
+            raise ValueError("the asset covariance needs specific volatilities: pass a tensor "
+                             "[N] / [D_loc, N] or 'shrunk'")
+        if isinstance(specific_vol, str):
+            specific_vol = self.specific_risk_shrunk()
+        return cov, specific_vol.to(self.device)
+
+    def _rows(self, h: torch.Tensor) -> torch.Tensor:
+        h = h.to(device=self.device, dtype=torch.float64)
+        return h[None, :].expand(self.panel.D, -1) if h.dim() == 1 else h
+
+    def solve_cov(self, b: torch.Tensor, which: str = "vra",
+                  specific_vol: torch.Tensor | str = "shrunk",
+                  universe: torch.Tensor | None = None) -> torch.Tensor:
+        """``Sigma_d^-1 b`` on this rank's dates for the asset covariance ``Sigma_d = X_d F_d X_d^T
+        + diag(s_d^2)`` (:mod:`ops.factor_cov`: Woodbury, no N x N matrix).  ``b`` is [N] (the
+        same every date), [D_loc, N] or [D_loc, NB, N]; ``which`` / ``specific_vol`` as in
+        :meth:`risk_attribution`; ``universe`` an optional [D_loc, N] bool mask.  Stocks outside
+        the universe get 0, dates with an invalid covariance NaN.  Per date: the only collective
+        is the one ``"shrunk"`` makes."""
+        from ..ops import factor_cov as fc
+        cov, sv = self._cov_inputs(which, specific_vol)
+        p = self.panel
+        return fc.solve_cov(p.styles, p.cap, p.ret, p.ind, self.stats, p.P, cov, sv,
+                            self._rows(b), universe)
+
+    def apply_cov(self, h: torch.Tensor, which: str = "vra",
+                  specific_vol: torch.Tensor | str = "shrunk",
+                  universe: torch.Tensor | None = None) -> torch.Tensor:
+        """``Sigma_d h`` restricted to the universe; arguments as :meth:`solve_cov`."""
+        from ..ops import factor_cov as fc
+        cov, sv = self._cov_inputs(which, specific_vol)
+        p = self.panel
+        return fc.apply_cov(p.styles, p.cap, p.ret, p.ind, self.stats, p.P, cov, sv,
+                            self._rows(h), universe)
+
+    def min_variance(self, which: str = "vra", specific_vol: torch.Tensor | str = "shrunk",
+                     universe: torch.Tensor | None = None):
+        """Fully invested, unconstrained minimum-variance portfolio of every date:
+        ``weights`` [D_loc, N] = y / sum(y) with y = Sigma^-1 1_U, and its ``variance`` [D_loc]
+        = 1 / sum(y).  NaN on dates with an invalid covariance or an empty universe."""
+        p = self.panel
+        ones = torch.ones(p.D, p.N, dtype=torch.float64, device=self.device)
+        y = self.solve_cov(ones, which, specific_vol, universe)
+        tot = y.sum(-1)
+        tot = torch.where(tot > 0, tot, torch.full_like(tot, float("nan")))
+        return MinVariance(weights=y / tot[:, None], variance=1.0 / tot)
+
+    def predicted_beta(self, h_bench: torch.Tensor, which: str = "vra",
+                       specific_vol: torch.Tensor | str = "shrunk",
+                       universe: torch.Tensor | None = None) -> torch.Tensor:
+        """Predicted beta of every stock to the benchmark holdings ``h_bench`` ([N] or
+        [D_loc, N]): ``Sigma h_b / (h_b^T Sigma h_b)`` [D_loc, N], NaN outside the universe."""
+        from ..ops import factor_cov as fc
+        cov, sv = self._cov_inputs(which, specific_vol)
+        p = self.panel
+        h = self._rows(h_bench)
+        Sh = fc.apply_cov(p.styles, p.cap, p.ret, p.ind, self.stats, p.P, cov, sv, h, universe)
+        m = fc.universe_mask(p.styles, p.cap, p.ret, p.ind, p.P, sv, universe)
+        hz = torch.where(m, torch.nan_to_num(h, nan=0.0, posinf=0.0, neginf=0.0),
+                         torch.zeros_like(Sh))
+        beta = Sh / (hz * Sh).sum(-1, keepdim=True)
+        return torch.where(m, beta, torch.full_like(beta, float("nan")))
 
     # --------------------------------------------------------------- pandas views
     def factor_returns_frame(self):

@@ -1,0 +1,393 @@
+"""Factor-structured covariance solve (``ops.factor_cov``, ``csrc/factor_cov.hip``) and the
+portfolio-construction methods of ``RiskModel`` (min-variance weights, predicted beta).
+
+The oracle of the CPU tests is dense: the explicit design matrix ``X_d``, ``Sigma = X F X^T +
+diag(s^2)`` on the universe and ``torch.linalg.solve``.  For the synthetic inputs used here
+cond(Sigma) <= 1.5e3 and the Woodbury form agrees with the dense solve to <= 7e-14 of the
+column's max, so the 1e-10 / 1e-9 bounds below sit four orders of magnitude above the algebra's
+own error.  The GPU tests compare every kernel with the CPU path.
+"""
+import functools
+import os
+import socket
+import tempfile
+
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from llm_driven_multi_factor_model_amd.models.panel import synthetic_panel
+from llm_driven_multi_factor_model_amd.ops import factor_cov as fc
+from llm_driven_multi_factor_model_amd.ops.cross_section import valid_mask, xs_wls
+
+F64 = torch.float64
+
+
+class Case:
+    """Seeded kernel-level inputs: panel + stats, F = A^T A / (3K) with A = 0.01 randn(3K, K),
+    s = 0.01 + 0.03 rand(N), NB right-hand sides."""
+
+    def __init__(self, D, N, P, Q, NB=3, dtype=torch.float32, seed=3, edge=False, rank_def=None):
+        p = synthetic_panel(D, N, P, Q, seed=seed, missing_frac=0.03, dtype=dtype)
+        self.p, self.D, self.N, self.P, self.Q, self.NB = p, D, N, P, Q, NB
+        self.K = K = 1 + P + Q
+        self.stats = xs_wls(p.styles, p.cap, p.ret, p.ind, P).stats
+        g = torch.Generator().manual_seed(1000 + seed)
+        A = 0.01 * torch.randn(D, 3 * K, K, generator=g, dtype=F64)
+        self.F = A.transpose(1, 2) @ A / (3 * K)
+        self.s = 0.01 + 0.03 * torch.rand(N, generator=g, dtype=F64)
+        self.rhs = torch.randn(D, NB, N, generator=g, dtype=F64)
+        self.universe = None
+        if rank_def is not None:
+            self.F[rank_def] = _drop_smallest(self.F[rank_def], 5)
+        if edge:
+            self.F[1] = _drop_smallest(self.F[1], 5)   # rank-deficient by 5
+            self.F[2] = float("nan")                   # an invalid date
+            self.s = self.s.clone()
+            self.s[5::17] = float("nan")
+            self.s[9::23] = 0.0
+            self.universe = torch.ones(D, N, dtype=torch.bool)
+            self.universe[:, ::3] = False
+            self.rhs[0, 0, 7] = float("nan")
+            self.rhs[3, -1, 100:110] = float("nan")
+
+    @property
+    def panel_args(self):
+        p = self.p
+        return p.styles, p.cap, p.ret, p.ind, self.stats, self.P
+
+    def on(self, dev):
+        p = self.p.to(dev)
+        return p.styles, p.cap, p.ret, p.ind, self.stats.to(dev), self.P
+
+
+def _drop_smallest(F, k):
+    w, U = torch.linalg.eigh(F)
+    w[:k] = 0.0
+    return (U * w) @ U.T
+
+
+@functools.lru_cache(maxsize=None)
+def _case(*a, **kw):
+    return Case(*a, **dict(kw))
+
+
+def _dense_X(p, stats, P):
+    """Explicit design matrix [D, N, K] (zero rows for invalid stocks), as attribution's oracle."""
+    X = p.styles
+    D, Q, N = X.shape
+    m = valid_mask(X, p.cap, p.ret, p.ind, P)
+    mu, sig = stats[:, :Q].double(), stats[:, Q].double()
+    Z = (X.double() - mu[:, :, None]) / sig[:, None, None]
+    cols = [torch.ones(D, N, 1, dtype=F64)]
+    if P > 0:
+        cols.append(torch.nn.functional.one_hot(p.ind.long().clamp(0, P - 1), P).double())
+    cols.append(Z.transpose(1, 2))
+    Xd = torch.cat(cols, 2)
+    return torch.where(m[..., None], Xd, torch.zeros((), dtype=F64)), m
+
+
+def _dense(c: Case):
+    """(solve, product, universe mask): Sigma^-1 b and Sigma b by dense N x N algebra per date."""
+    Xd, m = _dense_X(c.p, c.stats, c.P)
+    s = c.s[None, :].expand(c.D, c.N) if c.s.dim() == 1 else c.s
+    m = m & torch.isfinite(s) & (s > 0)
+    if c.universe is not None:
+        m = m & c.universe
+    b = torch.nan_to_num(c.rhs, nan=0.0)
+    sol = torch.zeros(c.D, c.NB, c.N, dtype=F64)
+    prod = torch.zeros(c.D, c.NB, c.N, dtype=F64)
+    for d in range(c.D):
+        if not torch.isfinite(c.F[d]).all():
+            sol[d] = prod[d] = float("nan")
+            continue
+        idx = torch.nonzero(m[d]).flatten()
+        Xu = Xd[d, idx]
+        Sig = Xu @ c.F[d] @ Xu.T + torch.diag(s[d, idx] ** 2)
+        bu = b[d][:, idx].T
+        sol[d][:, idx] = torch.linalg.solve(Sig, bu).T
+        prod[d][:, idx] = (Sig @ bu).T
+    return sol, prod, m
+
+
+def _assert_rel(got, ref, rel, what):
+    """Per (date, rhs) row: max abs error <= rel x max |ref|; NaN and exact-0 patterns equal."""
+    assert got.shape == ref.shape, what
+    assert torch.equal(torch.isnan(got), torch.isnan(ref)), f"{what}: NaN pattern"
+    assert torch.equal(got == 0, ref == 0), f"{what}: zero pattern"
+    g, r = torch.nan_to_num(got), torch.nan_to_num(ref)
+    err = (g - r).abs().amax(-1)
+    scale = r.abs().amax(-1)
+    worst = (err / scale.clamp(min=1e-300)).max().item()
+    print(f"{what}: worst relative error {worst:.2e} (bound {rel:.0e})")
+    assert (err <= rel * scale).all(), f"{what}: {worst:.3e} > {rel:.0e}"
+
+
+# ------------------------------------------------------------------------------------ CPU
+@pytest.mark.parametrize("shape", [(4, 203, 5, 4), (2, 77, 0, 3)])
+def test_solve_cov_matches_dense(shape):
+    c = _case(*shape)
+    sol, _, m = _dense(c)
+    got = fc.solve_cov(*c.panel_args, c.F, c.s, c.rhs)
+    _assert_rel(got, sol, 1e-10, "solve_cov")
+    assert (got[~m[:, None, :].expand_as(got)] == 0).all()
+    # a [D, N] right-hand side gives a [D, N] result
+    one = fc.solve_cov(*c.panel_args, c.F, c.s, c.rhs[:, 1])
+    assert one.shape == (c.D, c.N)
+    _assert_rel(one, got[:, 1], 1e-12, "[D, N] rhs")
+
+
+def test_solve_cov_edge_cases():
+    c = _case(4, 203, 5, 4, edge=True)
+    sol, prod, m = _dense(c)
+    got = fc.solve_cov(*c.panel_args, c.F, c.s, c.rhs, c.universe)
+    assert torch.isnan(got[2]).all() and torch.isfinite(got[[0, 1, 3]]).all()
+    _assert_rel(got, sol, 1e-10, "solve_cov edge")
+    ok = [0, 1, 3]
+    assert (got[ok][~m[ok][:, None, :].expand(-1, c.NB, -1)] == 0).all()
+    assert not m[:, ::3].any() and not m[:, 5::17].any() and not m[:, 9::23].any()
+    _assert_rel(fc.apply_cov(*c.panel_args, c.F, c.s, c.rhs, c.universe), prod, 1e-12,
+                "apply_cov edge")
+    # per-date specific volatilities [D, N] are the same thing
+    got2 = fc.solve_cov(*c.panel_args, c.F, c.s[None].expand(c.D, -1), c.rhs, c.universe)
+    _assert_rel(got2, got, 1e-12, "[D, N] specific volatilities")
+    # a non-finite stats row invalidates its date only
+    st = c.stats.clone()
+    st[0, 1] = float("nan")
+    p = c.p
+    got3 = fc.solve_cov(p.styles, p.cap, p.ret, p.ind, st, c.P, c.F, c.s, c.rhs, c.universe)
+    assert torch.isnan(got3[0]).all()
+    _assert_rel(got3[1], got[1], 1e-12, "date next to a NaN stats row")
+
+
+@pytest.mark.parametrize("shape", [(4, 203, 5, 4), (2, 77, 0, 3)])
+def test_apply_cov_and_round_trip(shape):
+    c = _case(*shape)
+    _, prod, m = _dense(c)
+    got = fc.apply_cov(*c.panel_args, c.F, c.s, c.rhs)
+    _assert_rel(got, prod, 1e-12, "apply_cov")
+    back = fc.apply_cov(*c.panel_args, c.F, c.s, fc.solve_cov(*c.panel_args, c.F, c.s, c.rhs))
+    bu = torch.where(m[:, None, :], c.rhs, torch.zeros((), dtype=F64))
+    _assert_rel(back, bu, 1e-9, "apply_cov(solve_cov(b))")
+
+
+def _risk_model(device="cpu"):
+    from llm_driven_multi_factor_model_amd.models.risk_model import RiskModel
+    from llm_driven_multi_factor_model_amd.utils.config import preset
+    p = synthetic_panel(60, 80, 4, 3, seed=5, missing_frac=0.02)
+    return RiskModel(p.to(device), preset("reference", eigen_sims=5)).run()
+
+
+def test_risk_model_min_variance_and_beta_cpu():
+    m = _risk_model()
+    p = m.panel
+    mv = m.min_variance()
+    w, var = mv.weights, mv.variance
+    assert w.shape == (p.D, p.N) and var.shape == (p.D,)
+    fin = torch.isfinite(w).all(-1)
+    assert fin[-10:].all() and torch.equal(fin, torch.isfinite(var))
+    torch.testing.assert_close(w[fin].sum(-1), torch.ones(int(fin.sum()), dtype=F64),
+                               rtol=1e-12, atol=0)
+    sv = m.specific_risk_shrunk()
+    U = fc.universe_mask(p.styles, p.cap, p.ret, p.ind, p.P, sv)
+    assert (w[fin][~U[fin]] == 0).all()
+    # first-order condition: Sigma w is constant over the universe and equals the variance
+    Sw = m.apply_cov(w)
+    dev = torch.where(U, (Sw - var[:, None]).abs(), torch.zeros((), dtype=F64))[fin]
+    assert (dev.amax(-1) <= 1e-9 * var[fin]).all(), (dev.amax(-1) / var[fin]).max()
+    # no fully invested portfolio on the universe has less variance: equal weights do not
+    h_eq = U.double() / U.sum(-1, keepdim=True).clamp(min=1)
+    tv = m.risk_attribution(h_eq).total_var
+    assert (var[fin] <= tv[fin] * (1 + 1e-12)).all() and (var[fin] > 0).all()
+    # predicted beta of the benchmark to itself is 1
+    hb = torch.full((p.N,), 1.0 / p.N, dtype=F64)
+    hb[::3] *= 2.0
+    beta = m.predicted_beta(hb)
+    assert torch.equal(torch.isfinite(beta), U & fin[:, None])
+    s = torch.nan_to_num(beta * hb[None]).sum(-1)[fin]
+    torch.testing.assert_close(s, torch.ones_like(s), rtol=1e-10, atol=0)
+    # other covariance series and explicit specific volatilities go through the same path
+    y = m.solve_cov(torch.ones(p.N, dtype=F64), which="nw", specific_vol=sv)
+    assert y.shape == (p.D, p.N)
+    with pytest.raises(ValueError):
+        m.solve_cov(torch.ones(p.N, dtype=F64), specific_vol=None)
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+def _dist_panel():
+    return synthetic_panel(37, 64, 4, 3, seed=21, missing_frac=0.05)
+
+
+def _dist_outputs(m):
+    hb = torch.full((m.panel.N,), 1.0 / m.panel.N, dtype=F64)
+    hb[::3] *= 2.0
+    mv = m.min_variance()
+    return dict(weights=mv.weights, variance=mv.variance, beta=m.predicted_beta(hb))
+
+
+def _dist_worker(rank, world, port, path):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
+                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    from llm_driven_multi_factor_model_amd.models.risk_model import RiskModel
+    from llm_driven_multi_factor_model_amd.parallel import dist as pdist
+    from llm_driven_multi_factor_model_amd.utils.config import preset
+    ctx = pdist.init_distributed(device="cpu")
+    full = _dist_panel()
+    a, b = pdist.shard_range(full.D, ctx.rank, ctx.world)
+    m = RiskModel(full.slice_dates(a, b), preset("reference", eigen_sims=5), T_global=full.D,
+                  ctx=ctx).run()
+    got = {k: pdist.gather_to_root(v.contiguous(), ctx) for k, v in _dist_outputs(m).items()}
+    if ctx.rank == 0:
+        torch.save(got, path)
+    pdist.barrier(ctx)
+    torch.distributed.destroy_process_group()
+
+
+def test_min_variance_and_beta_rank_invariant():
+    from llm_driven_multi_factor_model_amd.models.risk_model import RiskModel
+    from llm_driven_multi_factor_model_amd.utils.config import preset
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "fc.pt")
+        mp.spawn(_dist_worker, args=(2, _free_port(), path), nprocs=2, join=True)
+        got = torch.load(path, weights_only=True)
+    ref = _dist_outputs(RiskModel(_dist_panel(), preset("reference", eigen_sims=5)).run())
+    assert torch.isfinite(ref["weights"][-5:]).all()
+    for k, v in ref.items():
+        torch.testing.assert_close(got[k], v, rtol=1e-12, atol=1e-15, equal_nan=True, msg=k)
+
+
+def test_zero_date_shard_returns_empty():
+    c = _case(4, 203, 5, 4)
+    p = c.p.slice_dates(0, 0)
+    out = fc.solve_cov(p.styles, p.cap, p.ret, p.ind, c.stats[:0], c.P, c.F[:0], c.s, c.rhs[:0])
+    assert out.shape == (0, c.NB, c.N)
+    out = fc.apply_cov(p.styles, p.cap, p.ret, p.ind, c.stats[:0], c.P, c.F[:0], c.s,
+                       c.rhs[:0, 0])
+    assert out.shape == (0, c.N)
+
+
+# ------------------------------------------------------------------------------------ GPU
+GPU_CASES = [
+    # D, N, P, Q, NB, dtype, kwargs
+    pytest.param(5, 203, 5, 4, 1, torch.float64, (), id="ragged-f64-nb1"),
+    pytest.param(5, 203, 5, 4, 9, torch.float32, (), id="ragged-f32-nb9"),
+    pytest.param(3, 1000, 31, 10, 3, torch.float64, (), id="k42-f64-nb3"),
+    pytest.param(3, 1000, 31, 10, 9, torch.float32, (), id="k42-f32-nb9"),
+    pytest.param(3, 300, 53, 10, 9, torch.float32, (("rank_def", 1),), id="k64-rankdef-nb9"),
+    pytest.param(2, 77, 0, 3, 3, torch.float32, (), id="no-industries-nb3"),
+    pytest.param(2, 130, 3, 16, 1, torch.float32, (), id="q16-blocked-nb1"),
+    pytest.param(4, 203, 5, 4, 3, torch.float32, (("edge", True),), id="edge-cases-nb3"),
+]
+
+
+def _check_kernels(c: Case, dev):
+    cpu, gpu = c.panel_args, c.on(dev)
+    uni = None if c.universe is None else c.universe.to(dev)
+    a, s2 = fc._weights(*cpu[:4], c.P, c.s, c.universe)
+    # weighted factor Gram: 1e-11 of max |G| per date
+    G = fc.factor_gram(*cpu, a)
+    Gg = fc.factor_gram(*gpu, a.to(dev)).cpu()
+    _assert_rel(Gg.reshape(c.D, -1), G.reshape(c.D, -1), 1e-11, "factor_gram")
+    # Woodbury inner solve on the CPU path's G and g
+    b0 = torch.nan_to_num(c.rhs, nan=0.0)
+    # g = X^T (a o b): sums of N <= 1000 fp64 terms whose worst-case rounding bound is
+    # N eps sum|t| ~ N^1.5 eps max|g| = 3.5e-12 max|g| for random-sign terms, so 1e-11 holds
+    g = fc.factor_xty(*cpu, a[:, None] * b0)
+    _assert_rel(fc.factor_xty(*gpu, (a[:, None] * b0).to(dev)).cpu(), g, 1e-11, "factor_xty")
+    coef = fc.woodbury_coef(G, c.F, g)
+    coef_g = fc.woodbury_coef(G.to(dev), c.F.to(dev), g.to(dev)).cpu()
+    _assert_rel(coef_g, coef, 1e-9, "woodbury_coef")
+    # apply on the CPU path's c, both (u, v) conventions
+    for u, v, what in ((a, -a, "inverse"), (s2, (a > 0).double(), "forward")):
+        ref = fc.factor_apply(*cpu, u, v, c.rhs, coef)
+        got = fc.factor_apply(*gpu, u.to(dev), v.to(dev), c.rhs.to(dev), coef.to(dev)).cpu()
+        _assert_rel(got, ref, 1e-9, f"factor_apply {what}")
+    # end to end
+    ref = fc.solve_cov(*cpu, c.F, c.s, c.rhs, c.universe)
+    got = fc.solve_cov(*gpu, c.F.to(dev), c.s.to(dev), c.rhs.to(dev), uni).cpu()
+    _assert_rel(got, ref, 1e-9, "solve_cov")
+    ref = fc.apply_cov(*cpu, c.F, c.s, c.rhs, c.universe)
+    got = fc.apply_cov(*gpu, c.F.to(dev), c.s.to(dev), c.rhs.to(dev), uni).cpu()
+    _assert_rel(got, ref, 1e-9, "apply_cov")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D,N,P,Q,NB,dtype,kw", GPU_CASES)
+def test_hip_kernels_match_cpu_path(cuda, D, N, P, Q, NB, dtype, kw):
+    _check_kernels(_case(D, N, P, Q, NB=NB, dtype=dtype, **dict(kw)), cuda)
+
+
+@pytest.mark.gpu
+def test_hip_bitwise_reproducible(cuda):
+    """Every reduction of the four kernels runs in a fixed order (wave-owned LDS tables summed in
+    wave order, no cross-wave float atomics), so two runs give the same bits."""
+    c = _case(3, 1000, 31, 10, NB=3, dtype=torch.float64)
+    gpu = c.on(cuda)
+    a = fc._weights(*gpu[:4], c.P, c.s.to(cuda), None)[0]
+    assert torch.equal(fc.factor_gram(*gpu, a), fc.factor_gram(*gpu, a))
+    F, s, rhs = c.F.to(cuda), c.s.to(cuda), c.rhs.to(cuda)
+    assert torch.equal(fc.solve_cov(*gpu, F, s, rhs), fc.solve_cov(*gpu, F, s, rhs))
+    assert torch.equal(fc.apply_cov(*gpu, F, s, rhs), fc.apply_cov(*gpu, F, s, rhs))
+
+
+@pytest.mark.gpu
+def test_hip_limits_raise_before_launch(cuda):
+    D, N, P, Q = 1, 16, 54, 10   # K = 65
+    K = 1 + P + Q
+    X = torch.zeros(D, Q, N, device=cuda)
+    v = torch.zeros(D, N, device=cuda)
+    ind = torch.zeros(D, N, dtype=torch.int16, device=cuda)
+    st = torch.ones(D, Q + 2, dtype=F64, device=cuda)
+    F = torch.eye(K, dtype=F64, device=cuda)[None]
+    d = v.double()
+    with pytest.raises(ValueError, match="64"):
+        fc.solve_cov(X, v, v, ind, st, P, F, d[0] + 1, d)
+    with pytest.raises(ValueError, match="64"):
+        fc.apply_cov(X, v, v, ind, st, P, F, d[0] + 1, d)
+    with pytest.raises(ValueError, match="64"):
+        fc.factor_gram(X, v, v, ind, st, P, d)
+    with pytest.raises(ValueError, match="64"):
+        fc.factor_xty(X, v, v, ind, st, P, d[:, None])
+    with pytest.raises(ValueError, match="64"):
+        fc.woodbury_coef(F, F, torch.zeros(D, 1, K, dtype=F64, device=cuda))
+    with pytest.raises(ValueError, match="64"):
+        fc.factor_apply(X, v, v, ind, st, P, d, d, d[:, None], torch.zeros(D, 1, K, dtype=F64,
+                                                                          device=cuda))
+    X17 = torch.zeros(D, 17, N, device=cuda)   # Q = 17 > 16 styles
+    with pytest.raises(ValueError, match="16"):
+        fc.factor_gram(X17, v, v, None, torch.ones(D, 19, dtype=F64, device=cuda), 0, d)
+
+
+@pytest.mark.gpu
+def test_risk_model_gpu_matches_cpu(cuda):
+    """``min_variance`` / ``predicted_beta`` of a GPU model against the same model on the CPU.
+    The Newey-West series is compared between two independent runs; the eigen-adjusted series
+    draw their simulations from different generators on the two devices, so for ``vra`` the CPU
+    model is given the GPU model's covariances (the solve itself is what is compared)."""
+    from llm_driven_multi_factor_model_amd.models.risk_model import RiskModel
+    from llm_driven_multi_factor_model_amd.utils.config import preset
+    p = synthetic_panel(80, 520, 31, 10, seed=5, missing_frac=0.03)
+    cfg = preset("reference", eigen_sims=5)
+    mc = RiskModel(p, cfg).run()
+    mg = RiskModel(p.to(cuda), cfg).run()
+    mc.eigen_cov, mc.vra_cov = mg.eigen_cov.cpu(), mg.vra_cov.cpu()
+    hb = (p.cap[-1] / p.cap[-1].sum()).double()
+    for which in ("nw", "vra"):
+        rc, rg = mc.min_variance(which), mg.min_variance(which)
+        bc, bg = mc.predicted_beta(hb, which), mg.predicted_beta(hb.to(cuda), which).cpu()
+        fin_c = torch.isfinite(rc.weights).all(-1)
+        assert torch.equal(fin_c, torch.isfinite(rg.weights).all(-1).cpu()), which
+        assert fin_c[-10:].all()
+        assert torch.equal(torch.isfinite(bc), torch.isfinite(bg)), which
+        _assert_rel(rg.weights.cpu()[fin_c], rc.weights[fin_c], 1e-8, f"{which} weights")
+        _assert_rel(rg.variance.cpu()[fin_c][:, None], rc.variance[fin_c][:, None], 1e-8,
+                    f"{which} variance")
+        _assert_rel(torch.nan_to_num(bg)[fin_c], torch.nan_to_num(bc)[fin_c], 1e-8,
+                    f"{which} beta")

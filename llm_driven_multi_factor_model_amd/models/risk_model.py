@@ -37,6 +37,18 @@ class MinVariance(NamedTuple):
     variance: torch.Tensor
 
 
+class Portfolio(NamedTuple):
+    """:meth:`RiskModel.optimize`: ``weights`` [D_loc, N], ``variance`` [D_loc] (float64),
+    ``passes`` / ``status`` [D_loc] (int32, the codes of :mod:`ops.box_qp`), ``active_variance``
+    [D_loc] (None without a benchmark), ``expected_return`` [D_loc] (None without alpha)."""
+    weights: torch.Tensor
+    variance: torch.Tensor
+    passes: torch.Tensor
+    status: torch.Tensor
+    active_variance: torch.Tensor | None
+    expected_return: torch.Tensor | None
+
+
 class RiskModel:
     """Barra risk model over a (possibly date-sharded) panel.
 
@@ -461,6 +473,45 @@ class RiskModel:
         tot = y.sum(-1)
         tot = torch.where(tot > 0, tot, torch.full_like(tot, float("nan")))
         return MinVariance(weights=y / tot[:, None], variance=1.0 / tot)
+
+    def optimize(self, alpha: torch.Tensor | None = None, risk_aversion: float = 1.0,
+                 lower=0.0, upper=1.0, benchmark: torch.Tensor | None = None, budget=1.0,
+                 which: str = "vra", specific_vol: torch.Tensor | str = "shrunk",
+                 universe: torch.Tensor | None = None, **solver) -> Portfolio:
+        """Box-constrained portfolio of every date (:func:`ops.box_qp.box_qp`): minimise
+        ``1/2 h^T Sigma h - q^T h`` subject to ``sum h = budget`` and ``lower <= h <= upper`` on
+        the universe, with ``q = alpha / risk_aversion`` (+ ``Sigma h_b`` when a ``benchmark`` is
+        given: minimum tracking error, or a mean-variance tilt around it).  ``alpha`` /
+        ``benchmark`` are [N] or [D_loc, N]; ``lower`` / ``upper`` a scalar, [N] or [D_loc, N];
+        ``which`` / ``specific_vol`` / ``universe`` as in :meth:`min_variance`; ``solver``
+        passes ``tol``, ``max_passes`` and ``check_every`` on.  Infeasible dates and dates with
+        an invalid covariance give NaN rows (see ``status``).  Per date: the only collective is
+        the one ``"shrunk"`` makes."""
+        from ..ops import box_qp as bq
+        from ..ops import factor_cov as fc
+        cov, sv = self._cov_inputs(which, specific_vol)
+        p = self.panel
+        args = (p.styles, p.cap, p.ret, p.ind, self.stats, p.P)
+        q = torch.zeros(p.D, p.N, dtype=torch.float64, device=self.device)
+        al = hb = Shb = None
+        if alpha is not None:
+            al = torch.nan_to_num(self._rows(alpha), nan=0.0, posinf=0.0, neginf=0.0)
+            q = q + al / risk_aversion
+        if benchmark is not None:
+            hb = self._rows(benchmark)
+            Shb = fc.apply_cov(*args, cov, sv, hb, universe)
+            q = q + Shb
+        r = bq.box_qp(*args, cov, sv, q, lower, upper, budget, universe, **solver)
+        active = ret = None
+        if hb is not None:   # (h - h_b)^T Sigma (h - h_b), h_b restricted to the universe
+            m = fc.universe_mask(p.styles, p.cap, p.ret, p.ind, p.P, sv, universe)
+            hz = torch.where(m, torch.nan_to_num(hb, nan=0.0, posinf=0.0, neginf=0.0),
+                             torch.zeros_like(q))
+            e = r.weights - hz   # formed from the difference: no cancellation of variances
+            active = (e * fc.apply_cov(*args, cov, sv, e, universe)).sum(-1)
+        if al is not None:
+            ret = (al * r.weights).sum(-1)
+        return Portfolio(r.weights, r.variance, r.passes, r.status, active, ret)
 
     def predicted_beta(self, h_bench: torch.Tensor, which: str = "vra",
                        specific_vol: torch.Tensor | str = "shrunk",

@@ -10,7 +10,10 @@
 //   bayes_shrink   Barra-master/mfm/utils.py:133-168          (cap-decile Bayesian shrinkage)
 //
 // Layout: field panels are [F][D][N] fp32 (each (field, date) row contiguous).  One workgroup
-// per (field, date) row or per date; fp64 accumulation; deterministic (no float atomics).
+// per (field, date) row or per date; fp64 accumulation; deterministic: every sum is a fixed-order
+// wave or block tree and no kernel in this file uses an atomic.
+// Limits: composite C <= 8, ols_resid p <= 4, style_norm Q <= 64, bayes_shrink G <= 64 and
+// N <= 16384 for the in-LDS sort (any N through the presorted entry point).
 #include "common.h"
 
 namespace {
@@ -126,15 +129,20 @@ __global__ __launch_bounds__(256) void ols_resid_kernel(const float* __restrict_
     for (int i = 0; i < 5; ++i)
       for (int j = i; j < 5; ++j) { G[i][j] = acc[idx]; G[j][i] = acc[idx]; ++idx; }
     for (int i = 0; i < 5; ++i) G[i][5] = acc[15 + i];
-    // Gauss-Jordan with partial pivoting on the m x m system (pinv semantics for exact zeros)
+    // Gauss-Jordan on the symmetric positive semi-definite m x m normal equations, in column
+    // order without row exchanges (stable for a Gram matrix), so the pivot of column c is its
+    // Schur complement: what is left of z_c'z_c after projecting out the columns before it.
+    // A column whose pivot is at most 8 (n + 8) eps64 times its original diagonal (n = valid
+    // rows; n eps64 bounds the summation error of the Gram entries, the factor 8 covers the
+    // elimination) is linearly dependent on the earlier ones to working precision -- a constant,
+    // duplicated or all-zero regressor -- and is dropped (coefficient 0): the residual is then
+    // the projection residual that lstsq / pinv return for the rank-deficient date.
+    double d0[5];
+    for (int i = 0; i < 5; ++i) d0[i] = G[i][i];
+    const double rtol = 8.0 * (acc[20] + 8.0) * 2.220446049250313e-16;
     for (int c = 0; c < m; ++c) {
-      int piv = c;
-      for (int r = c + 1; r < m; ++r)
-        if (fabs(G[r][c]) > fabs(G[piv][c])) piv = r;
-      if (piv != c)
-        for (int k = 0; k <= 5; ++k) { const double t = G[c][k]; G[c][k] = G[piv][k]; G[piv][k] = t; }
       const double pv = G[c][c];
-      if (fabs(pv) < 1e-300) { for (int k = 0; k <= 5; ++k) G[c][k] = 0.0; continue; }
+      if (!(pv > rtol * d0[c])) { for (int k = 0; k <= 5; ++k) G[c][k] = 0.0; continue; }
       for (int k = 0; k <= 5; ++k) G[c][k] /= pv;
       for (int r = 0; r < m; ++r) {
         if (r == c) continue;
@@ -169,36 +177,39 @@ __global__ __launch_bounds__(256) void style_norm_kernel(float* __restrict__ X, 
   const int d = blockIdx.x;
   float* Xd = X + (size_t)d * Q * N;
   const float* cd = cap + (size_t)d * N;
-  double sc = 0.0, sx = 0.0, sxx = 0.0, cnt = 0.0;
+  double sc = 0.0, sx = 0.0, cnt = 0.0;
   for (int n = threadIdx.x; n < N; n += blockDim.x) {
     bool ok = fin(cd[n]);
     for (int q = 0; q < Q; ++q) ok = ok && fin(Xd[(size_t)q * N + n]);
     if (!ok) continue;
     sc += cd[n];
     cnt += 1.0;
-    for (int q = 0; q < Q; ++q) {
-      const double v = Xd[(size_t)q * N + n];
-      sx += v;
-      sxx = fma(v, v, sxx);
-    }
+    for (int q = 0; q < Q; ++q) sx += (double)Xd[(size_t)q * N + n];
   }
   sc = block_sum(sc, scratch);
   sx = block_sum(sx, scratch);
-  sxx = block_sum(sxx, scratch);
   cnt = block_sum(cnt, scratch);
+  // pooled std as np.std does it: squared deviations from the mean (E x^2 - m^2 loses
+  // (m / sd)^2 of the digits: 6 of 16 for styles with mean 100 and sd 0.1)
+  const double nq = cnt * Q, m = sx / nq;
+  double sdd = 0.0;
   for (int q = 0; q < Q; ++q) {
     double scx = 0.0;
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
       bool ok = fin(cd[n]);
       for (int k = 0; k < Q; ++k) ok = ok && fin(Xd[(size_t)k * N + n]);
-      if (ok) scx = fma((double)cd[n], (double)Xd[(size_t)q * N + n], scx);
+      if (ok) {
+        const double v = Xd[(size_t)q * N + n], dv = v - m;
+        scx = fma((double)cd[n], v, scx);
+        sdd = fma(dv, dv, sdd);
+      }
     }
     scx = block_sum(scx, scratch);
     if (threadIdx.x == 0) mus[q] = scx / sc;
   }
+  sdd = block_sum(sdd, scratch);
   __syncthreads();
-  const double nq = cnt * Q, m = sx / nq;
-  const double sig = sqrt(fmax(sxx / nq - m * m, 0.0));
+  const double sig = sqrt(sdd / nq);  // a date without a valid row: 0 / 0 = NaN, as np.std
   if (threadIdx.x == 0 && sig_out) sig_out[d] = sig;
   if (mu_out)
     for (int q = threadIdx.x; q < Q; q += blockDim.x) mu_out[(size_t)d * Q + q] = mus[q];
@@ -209,25 +220,37 @@ __global__ __launch_bounds__(256) void style_norm_kernel(float* __restrict__ X, 
     }
 }
 
-// ---- K11: cap-decile Bayesian shrinkage, one workgroup per date (N <= 8192).
+// ---- K11: cap-decile Bayesian shrinkage, one workgroup of 16 waves per date.
 // groups: pd.qcut(cap, G).codes (linear-interpolated quantile edges, right-closed bins, the
 // first bin includes the minimum); per group m = sum(vol*cap)/sum(cap), s = sqrt(mean((vol-m)^2));
 // out = v*m + (1-v)*|vol| with v = q|vol-m| / (q|vol-m| + s).
-// presorted != nullptr (wide universes, N > kBayesLdsN): the caller sorted each date's masked
-// caps (+inf = invalid) on the device and the edges are read from there instead of the LDS sort.
+// presorted == nullptr: N <= 16384 (BAYES_LDS_N of ops/xs_reduce.py); the date's masked caps (+inf = invalid) are
+// bitonic-sorted in dynamic LDS (4 bytes per key, padded to a power of two: 64 KB above
+// N = 8192, next to 3.6 KB static, for which the launcher raises the kernel's dynamic-LDS limit).
+// presorted != nullptr (wide universes, any N): the caller sorted each date's masked caps on the
+// device and the edges are read from there instead of the LDS sort.
+// The G - 1 inner edges are computed once into LDS with numpy's own arithmetic
+// (np.quantile(cap, np.linspace(0, 1, G + 1)), method "linear": virtual index (n - 1) * (g * (1 / G)),
+// lerp a + (b - a) t below t = 0.5 and b - (b - a)(1 - t) from there on, every operation rounded
+// on its own), so a cap that ties with an edge lands in the group pandas gives it.
+// Group sums are order-fixed (no atomics; see the loop): two calls give the same bits.
+// bayes_shrink at 2520 x 5000, G = 10 on one MI355X (tools/attr_prof.py --bayes-shrink 7: median of
+// 7 calls after a warm-up, the float32 conversions of its inputs included): 1.03 ms (min 1.01,
+// max 1.05); with floating-point LDS atomics for the group sums and the edges re-interpolated for every
+// element, as before: 1.17 ms (1.14 - 1.23).
 __global__ __launch_bounds__(1024) void bayes_shrink_kernel(const float* __restrict__ vol,
                                                             const float* __restrict__ cap, int N,
                                                             int G, double qq, float* __restrict__ out,
                                                             int* __restrict__ group_out,
                                                             const float* __restrict__ presorted) {
   extern __shared__ float lkeys[];  // [NP] sorted caps
-  __shared__ double gs[64][4];
+  __shared__ double gs[64][2];      // per group: cap-weighted mean, sqrt(mean squared deviation)
+  __shared__ double edges[64];      // edges[k], 1 <= k < G: upper edge of group k - 1
+  __shared__ int cs[16];
   const int d = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const float* vd = vol + (size_t)d * N;
   const float* cd = cap + (size_t)d * N;
   const float* keys = presorted ? presorted + (size_t)d * N : lkeys;
-  int nvalid = 0;
-  for (int g = tid; g < G * 4; g += nt) gs[g / 4][g % 4] = 0.0;
   if (!presorted) {
     int NP = 1;
     while (NP < N) NP <<= 1;
@@ -251,64 +274,85 @@ __global__ __launch_bounds__(1024) void bayes_shrink_kernel(const float* __restr
       }
   }
   __syncthreads();
+  int nvalid = 0;
   {
     int c = 0;
     for (int i = tid; i < N; i += nt) c += fin(keys[i]) ? 1 : 0;
-    __shared__ int cs[32];
     c = wave_sum(c);
     if ((tid & 63) == 0) cs[tid >> 6] = c;
     __syncthreads();
-    nvalid = 0;
     for (int w = 0; w < (nt + 63) / 64; ++w) nvalid += cs[w];
   }
-  // quantile edges (numpy 'linear'): e_g = sorted[(n-1) g / G] interpolated
-  auto edge = [&](int g) -> double {
-    const double pos = (double)(nvalid - 1) * g / G;
-    const int lo = (int)floor(pos);
+  if (tid >= 1 && tid < G && nvalid > 0) {
+    const double pos = __dmul_rn((double)(nvalid - 1), __dmul_rn((double)tid, 1.0 / (double)G));
+    const int lo = min((int)floor(pos), nvalid - 1);
     const int hi = min(lo + 1, nvalid - 1);
-    const double fr = pos - lo;
-    return (double)keys[lo] + ((double)keys[hi] - (double)keys[lo]) * fr;
-  };
-  int* grp = group_out ? group_out + (size_t)d * N : nullptr;
-  for (int i = tid; i < N; i += nt) {
-    int g = -1;
-    if (fin(cd[i]) && fin(vd[i])) {
-      const double c = cd[i];
-      g = 0;
-      for (int k = 1; k < G; ++k)
-        if (c > edge(k)) g = k;
-      atomicAdd(&gs[g][0], (double)vd[i] * c);
-      atomicAdd(&gs[g][1], c);
-    }
-    if (grp) grp[i] = g;
+    const double fr = pos - (double)lo;
+    const double a = keys[lo], b = keys[hi], ba = b - a;
+    edges[tid] = fr >= 0.5 ? __dsub_rn(b, __dmul_rn(ba, 1.0 - fr)) : __dadd_rn(a, __dmul_rn(ba, fr));
   }
   __syncthreads();
-  for (int i = tid; i < N; i += nt) {
-    if (!(fin(cd[i]) && fin(vd[i]))) continue;
-    const double c = cd[i];
+  auto group_of = [&](double c) -> int {
     int g = 0;
     for (int k = 1; k < G; ++k)
-      if (c > edge(k)) g = k;
-    const double mg = gs[g][0] / gs[g][1];
-    const double dv = (double)vd[i] - mg;
-    atomicAdd(&gs[g][2], dv * dv);
-    atomicAdd(&gs[g][3], 1.0);
+      if (c > edges[k]) g = k;
+    return g;
+  };
+  // group moments in a fixed order: thread t owns elements t, t + 1024, ... and keeps private
+  // partial sums for kGC groups at a time, wave_total adds the 64 lanes, thread j adds the 16 wave
+  // totals of group g0 + j in wave order.  Pass 0: sum(vol * cap), sum(cap) -> mean; pass 1:
+  // sum((vol - mean)^2), count -> s.
+  {
+    constexpr int kGC = 8;
+    __shared__ double ws[16][kGC][2];
+    const int lane = tid & 63, wv = tid >> 6, nw = (nt + 63) >> 6;
+    for (int pass = 0; pass < 2; ++pass)
+      for (int g0 = 0; g0 < G; g0 += kGC) {
+        double a0[kGC], a1[kGC];
+#pragma unroll
+        for (int j = 0; j < kGC; ++j) a0[j] = a1[j] = 0.0;
+        for (int i = tid; i < N; i += nt) {
+          if (!(fin(cd[i]) && fin(vd[i]))) continue;
+          const double c = cd[i], v = vd[i];
+          const int j = group_of(c) - g0;
+          if (j < 0 || j >= kGC) continue;
+          double x0 = v * c, x1 = c;
+          if (pass) {
+            const double dv = v - gs[g0 + j][0];
+            x0 = dv * dv;
+            x1 = 1.0;
+          }
+#pragma unroll
+          for (int k = 0; k < kGC; ++k)
+            if (j == k) { a0[k] += x0; a1[k] += x1; }
+        }
+#pragma unroll
+        for (int j = 0; j < kGC; ++j) {
+          const double t0 = wave_total(a0[j]), t1 = wave_total(a1[j]);
+          if (lane == 0) { ws[wv][j][0] = t0; ws[wv][j][1] = t1; }
+        }
+        __syncthreads();
+        if (tid < kGC && g0 + tid < G) {
+          double s0 = 0.0, s1 = 0.0;
+          for (int w = 0; w < nw; ++w) { s0 += ws[w][tid][0]; s1 += ws[w][tid][1]; }
+          gs[g0 + tid][pass] = pass ? sqrt(s0 / s1) : s0 / s1;
+        }
+        __syncthreads();
+      }
   }
-  __syncthreads();
+  int* grp = group_out ? group_out + (size_t)d * N : nullptr;
   for (int i = tid; i < N; i += nt) {
     float o = qnanf();
+    int g = -1;
     if (fin(cd[i]) && fin(vd[i])) {
-      const double c = cd[i];
-      int g = 0;
-      for (int k = 1; k < G; ++k)
-        if (c > edge(k)) g = k;
-      const double mg = gs[g][0] / gs[g][1];
-      const double sg = sqrt(gs[g][2] / gs[g][3]);
+      g = group_of((double)cd[i]);
+      const double mg = gs[g][0], sg = gs[g][1];
       const double a = qq * fabs((double)vd[i] - mg);
       const double v = a / (a + sg);
       o = (float)(v * mg + (1.0 - v) * fabs((double)vd[i]));
     }
     out[(size_t)d * N + i] = o;
+    if (grp) grp[i] = g;
   }
 }
 
@@ -359,7 +403,17 @@ MFA_API int mfa_bayes_shrink(const float* vol, const float* cap, int D, int N, i
   if (N > 16384 || G < 1 || G > 64) return (int)hipErrorInvalidValue;
   int NP = 1;
   while (NP < N) NP <<= 1;
-  hipLaunchKernelGGL(bayes_shrink_kernel, dim3(D), dim3(1024), NP * sizeof(float), (hipStream_t)stream,
+  const size_t lds = NP * sizeof(float);  // 64 KB for 8192 < N <= 16384, next to 3.6 KB static
+  // dynamic + static LDS pass 64 KB only at lds = 64 KB (N > 8192): raise the limit once, then
+  // larger requests go straight through (a gfx950 CU has 160 KB)
+  static size_t attr = 32 * 1024;
+  if (attr < lds) {
+    if (hipError_t err = hipFuncSetAttribute((const void*)bayes_shrink_kernel,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+      return (int)err;
+    attr = lds;
+  }
+  hipLaunchKernelGGL(bayes_shrink_kernel, dim3(D), dim3(1024), lds, (hipStream_t)stream,
                      vol, cap, N, G, q, out, groups, (const float*)nullptr);
   return (int)hipGetLastError();
 }

@@ -146,7 +146,9 @@ def _winsorize_ref(y: torch.Tensor, n_std: float) -> torch.Tensor:
     dev = torch.where(ok, v - mean, torch.zeros((), dtype=torch.float64))
     sd = torch.sqrt((dev * dev).sum(1, keepdim=True) / (c - 1))
     lo, hi = mean - n_std * sd, mean + n_std * sd
-    clipped = torch.minimum(torch.maximum(v, lo), hi)
+    # pandas clip: a NaN bound (an infinite value in the row) clips nothing (torch.maximum /
+    # minimum would propagate the NaN instead)
+    clipped = torch.where(v < lo, lo, torch.where(v > hi, hi, v))
     keep = (c >= 2).expand_as(v)
     return torch.where(ok & keep, clipped, v).float()
 
@@ -182,7 +184,9 @@ def ols_resid(y: torch.Tensor | None, xs: list[torch.Tensor], min_rows: int | No
     ``min_rows`` defaults to p + 2 (``orthogonalize_factors``); NLSIZE uses 2 and sign -1 with
     ``log_x0=True, ypow=3`` so SIZE = ln(total_mv) and SIZE^3 are formed in float64 in-kernel
     (as the reference does in numpy) instead of being rounded to float32 first.
-    Dates with fewer valid rows are all-NaN (the reference returns a NaN series).
+    Dates with fewer valid rows are all-NaN (the reference returns a NaN series).  On a
+    rank-deficient date (a constant, duplicated or all-zero regressor) the result is the
+    projection residual, as ``sm.OLS``' pinv gives it.
     """
     p = len(xs)
     if p > 4:
@@ -221,7 +225,13 @@ def _ols_resid_ref(y, xs, min_rows, sign, log_x0=False, ypow=0):
 
 # ------------------------------------------------------------------ z-score
 def style_norm(X: torch.Tensor, cap: torch.Tensor):
-    """``(x - cap-weighted mean_q) / pooled std`` for X [D, Q, N]; returns (Z, mu [D,Q], sigma [D])."""
+    """``(x - cap-weighted mean_q) / pooled std`` for X [D, Q, N]; returns (Z, mu [D,Q], sigma [D]).
+
+    A row enters the moments when its cap and all its Q styles are finite; the pooled std is
+    ``np.std`` of those values (squared deviations from their mean).  Every entry of the date is
+    transformed, those of excluded rows too (NaN stays NaN); a date without a valid row has NaN
+    ``mu`` / ``sigma`` and a NaN panel.  Q <= 64 on the GPU.
+    """
     Z = _f32(X).clone()
     cap = _f32(cap)
     D, Q, N = Z.shape
@@ -234,8 +244,11 @@ def style_norm(X: torch.Tensor, cap: torch.Tensor):
         mu = (Xz * w[:, None, :]).sum(2) / w.sum(1, keepdim=True)
         n = ok.sum(1).double() * Q
         m = Xz.sum((1, 2)) / n
-        sig = torch.sqrt(torch.clamp((Xz * Xz).sum((1, 2)) / n - m * m, min=0))
+        dev = torch.where(ok[:, None, :], Xd - m[:, None, None], torch.zeros((), dtype=torch.float64))
+        sig = torch.sqrt((dev * dev).sum((1, 2)) / n)   # np.std: two-pass, NaN without a valid row
         return ((Xd - mu[..., None]) / sig[:, None, None]).float(), mu, sig
+    if Q > 64:
+        raise ValueError("style_norm: at most 64 styles on the GPU")
     mu = torch.empty(D, Q, dtype=torch.float64, device=Z.device)
     sig = torch.empty(D, dtype=torch.float64, device=Z.device)
     _native.call("mfa_style_norm", _native.ptr(Z), _native.ptr(cap), D, Q, N, _native.ptr(mu),
@@ -244,7 +257,7 @@ def style_norm(X: torch.Tensor, cap: torch.Tensor):
 
 
 # ------------------------------------------------------------------ Bayesian shrinkage
-BAYES_LDS_N = 16384  # universes up to this size sort their caps in LDS
+BAYES_LDS_N = 16384  # universes up to this size sort their caps in LDS (64 KB of it above 8192)
 
 
 def bayes_shrink(volatility: torch.Tensor, capital: torch.Tensor, ngroup: int = 10, q: float = 1.0,

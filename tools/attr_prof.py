@@ -1,5 +1,9 @@
 """Where the risk-attribution stage spends its time (1 GPU, 2520 x 5000 fp64 panel): each
-sub-step of RiskModel.risk_attribution timed with HIP events (median of 5)."""
+sub-step of RiskModel.risk_attribution timed with HIP events (median of 5).
+
+``--bayes-shrink [CALLS]``: only ``bayes_shrink`` (the cap-decile shrink kernel of
+csrc/xs_reduce.hip) on the stage's own inputs, median / min / max of CALLS (7) calls after a
+warm-up."""
 import json
 import os
 import statistics
@@ -21,7 +25,7 @@ m = RiskModel(p, preset("reference")).run()
 h = torch.full((p.N,), 1.0 / p.N, device=dev, dtype=torch.float64)
 
 
-def t(fn, n=5):
+def t(fn, n=5, spread=False):
     fn()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -32,12 +36,20 @@ def t(fn, n=5):
         e1.record()
         e1.synchronize()
         v.append(e0.elapsed_time(e1))
+    if spread:
+        return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4),
+                "max_ms": round(max(v), 4), "calls": n}
     return round(statistics.median(v), 3)
 
 
 e = m.specific_ret.double()
 halo = pdist.halo_prev_rows(e, 251, m.ctx, m.sizes)
 vol = attr.trailing_vol(halo, e, 252, 1)
+if "--bayes-shrink" in sys.argv:
+    i = sys.argv.index("--bayes-shrink")
+    calls = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 7
+    print(json.dumps({"bayes_shrink": t(lambda: bayes_shrink(vol, p.cap.double(), 10, 1.0), calls, True)}))
+    sys.exit(0)
 H = h[None, :].expand(p.D, -1).contiguous()
 sv = m.specific_risk_shrunk()
 x = attr.portfolio_exposure(p.styles, p.cap, p.ret, p.ind, H, m.stats, p.P)

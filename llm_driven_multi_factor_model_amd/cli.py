@@ -4,7 +4,7 @@
     python -m llm_driven_multi_factor_model_amd.cli risk   --data data/barra_data_csi.csv \
         --industry data/industry_info.csv --out results/ [--preset reference] [--sims 100] \
         [--checkpoint risk.ckpt] [--resume risk.ckpt] [--attribution equal] [--mongo-uri URI] \
-        [--time-scan carry] [--no-deterministic] [--bias-stat 21 --bias-start 1000]
+        [--specific-model use4] [--time-scan carry] [--no-deterministic] [--bias-stat 21 --bias-start 1000]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m llm_driven_multi_factor_model_amd.cli risk ...
     python -m llm_driven_multi_factor_model_amd.cli factors --prices prices.csv --index index.csv \
         --industry sw_industry.csv --out data/
@@ -113,7 +113,8 @@ def cmd_risk(a):
         model.save(a.checkpoint)
     paths = write_risk_results(model, a.out, long_specific=a.long_specific)
     if a.attribution:
-        paths["risk_attribution"] = _write_attribution(model, a.attribution, a.out, ctx)
+        paths["risk_attribution"] = _write_attribution(model, a.attribution, a.out, ctx,
+                                                       a.specific_model)
     if a.bias_stat is not None:
         paths["eigenfactor_bias"] = _write_bias_stat(model, a.bias_stat, a.bias_start, a.out, ctx)
     if ctx.rank == 0:
@@ -123,11 +124,12 @@ def cmd_risk(a):
     pdist.barrier(ctx)
 
 
-def _write_attribution(model, spec: str, out_dir: str, ctx):
+def _write_attribution(model, spec: str, out_dir: str, ctx, specific_model: str = "trailing"):
     """Per-date risk decomposition of a portfolio: ``spec`` = "equal" (equal weight over the
     panel's stocks) or a CSV with columns ``stocknames, weight`` (held on every date).
     Writes ``risk_attribution.csv`` (rank 0): total / factor / specific volatility and the
-    country / industry / style / specific shares of variance."""
+    country / industry / style / specific shares of variance.  ``specific_model``: "trailing"
+    (the shrunk equal-weighted trailing vol) or "use4" (``RiskModel.specific_risk_use4``)."""
     from .parallel import dist as pdist
     N = model.panel.N
     if spec == "equal":
@@ -139,7 +141,8 @@ def _write_attribution(model, spec: str, out_dir: str, ctx):
         for s, v in zip(w["stocknames"].astype(str), w["weight"].astype(float)):
             if s in pos:
                 h[pos[s]] = v
-    r = model.risk_attribution(h.to(model.device))
+    r = model.risk_attribution(h.to(model.device),
+                               specific_vol="use4" if specific_model == "use4" else "shrunk")
     g = r.grouped(model.panel.P)
     cols = {"total_vol": torch.sqrt(r.total_var), "factor_vol": torch.sqrt(r.factor_var),
             "specific_vol": torch.sqrt(r.specific_var), **{f"{k}_share": v for k, v in g.items()}}
@@ -296,6 +299,9 @@ def main(argv=None):
                    help="first date of the bias statistic (MFM.py:203: 1000)")
     r.add_argument("--attribution", default=None,
                    help="'equal' or a CSV (stocknames, weight): write risk_attribution.csv")
+    r.add_argument("--specific-model", choices=["trailing", "use4"], default="trailing",
+                   help="specific risk behind --attribution: shrunk trailing vol, or the EW "
+                        "Newey-West vol with the specific volatility-regime multiplier")
     r.add_argument("--device", default=None, help="cpu to force the CPU path")
     r.add_argument("--long-specific", action="store_true")
     r.add_argument("--checkpoint", default=None, help="write a resumable checkpoint here")

@@ -82,6 +82,7 @@ class RiskModel:
         self.eigen_bias = None
         self.B2_global = self.B2 = None
         self.nw_params = None     # (q, tau) of the last newey_west() call
+        self.spec_vra_lambda = None   # [D_loc], set by specific_risk_use4()
 
     def _stage(self, name: str):
         return trace.stage(name, self.times, self.device, sync=self.sync_stages,
@@ -392,6 +393,68 @@ class RiskModel:
             return s
         return pdist.broadcast_last_row(s, self.ctx, self.sizes)
 
+    def specific_vol_ewnw(self, window: int = 252, half_life: float = 84.0, lags: int = 5,
+                          min_periods: int = 1) -> torch.Tensor:
+        """[D_loc, N] exponentially weighted, Newey-West corrected trailing specific volatility
+        (:func:`ops.specific_risk.ewnw_vol`): weights ``0.5 ** (age / half_life)`` and ``lags``
+        Bartlett-weighted autocovariances over the ``window`` dates ENDING at each date, with the
+        half-life and lag semantics of the factor covariance.  Point in time; the halo of the
+        preceding window - 1 rows crosses rank boundaries (one collective) and every window is
+        summed in its own fixed order, so the result is bitwise rank-invariant.  GPU: ``lags <=
+        5`` and ``window <= 1024``.  Checkpoints keep no specific returns: after a resume the
+        first window - 1 new dates see only new dates."""
+        from ..ops.specific_risk import ewnw_vol
+        e = self.specific_ret.double()
+        halo = pdist.halo_prev_rows(e, window - 1, self.ctx, self.sizes)
+        return ewnw_vol(halo, e, window, half_life, lags, min_periods)
+
+    def specific_risk_use4(self, window: int = 252, half_life: float = 84.0, lags: int = 5,
+                           ngroup: int = 10, q: float = 1.0, vra_half_life: float | None = None,
+                           out_of_sample: bool = True, per_date: bool = True):
+        """USE4-style specific risk: the cap-decile Bayesian shrinkage of
+        :meth:`specific_vol_ewnw`, times the specific volatility-regime multiplier lambda_S.
+
+        ``B2[t] = sum_n cap_n (e_tn / s_n)^2 / sum_n cap_n`` (:func:`ops.specific_risk.
+        spec_bias2`) tests the shrunk forecast ``s`` against the specific returns of date t:
+        the forecast made at t - 1 by default (``out_of_sample``; the first global date has
+        none, its B2 is NaN), that of date t itself otherwise.  ``lambda_S[t]^2`` is the
+        exponentially weighted mean (``vra_half_life``, default ``config.vra_half_life``) of
+        the B2 of all valid dates <= t, 1 while there is none; ``config.time_scan`` chooses the
+        carried scan or one all-gather, as for the factor VRA.  Returns ``s * lambda_S`` as
+        [D_loc, N] and keeps ``spec_vra_lambda`` [D_loc]; ``per_date=False``: [N] of the LAST
+        global date on every rank.  Collective in distributed mode.
+
+        A checkpoint keeps neither specific returns nor the B2 history of this model: after a
+        resume the windows and lambda_S start from the new dates."""
+        from ..ops.specific_risk import spec_bias2
+        from ..ops.xs_reduce import bayes_shrink
+        cap = self.panel.cap
+        s = bayes_shrink(self.specific_vol_ewnw(window, half_life, lags), cap.double(), ngroup,
+                         q).double()
+        e = self.specific_ret.double()
+        fc = s
+        if out_of_sample:
+            fc = torch.cat([pdist.halo_prev_rows(s, 1, self.ctx, self.sizes), s])[:s.shape[0]]
+        B2 = spec_bias2(e, fc, cap if cap.dtype == torch.float64 else cap.float())
+        tau = self.cfg.vra_half_life if vra_half_life is None else vra_half_life
+        if self.cfg.time_scan == "carry":
+            lam2 = ew_scan.ew_prefix_mean_sharded(B2, tau, self.ctx, self.sizes)
+        else:
+            lo = self.panel.date_offset
+            lam2 = ew_scan.ew_prefix_mean(pdist.all_gather_rows(B2, self.ctx, self.sizes), tau)[
+                lo:lo + self.panel.D]
+        lam2 = torch.nan_to_num(lam2, nan=1.0)   # no valid date yet: no adjustment
+        self.spec_vra_lambda = torch.sqrt(lam2)
+        out = s * self.spec_vra_lambda[:, None]
+        if per_date:
+            return out
+        return pdist.broadcast_last_row(out, self.ctx, self.sizes)
+
+    def _specific_vol_named(self, name: str) -> torch.Tensor:
+        """``specific_vol`` given as a string: ``"use4"`` is :meth:`specific_risk_use4`, every
+        other string :meth:`specific_risk_shrunk`."""
+        return self.specific_risk_use4() if name == "use4" else self.specific_risk_shrunk()
+
     def risk_attribution(self, h: torch.Tensor, which: str = "vra",
                          specific_vol: torch.Tensor | str | None = "shrunk"):
         """Risk decomposition of holdings ``h`` ([N] held every date, or [D_loc, N]) on this
@@ -399,8 +462,9 @@ class RiskModel:
 
         ``specific_vol``: per-stock specific volatility [N] or [D_loc, N]; ``"shrunk"`` uses
         :meth:`specific_risk_shrunk` (cap-decile Bayesian shrinkage of each date's own trailing
-        residual vol: point in time, identical for every world size; collective);
-        None ignores specific risk.  Returns :class:`ops.attribution.RiskAttribution`.
+        residual vol: point in time, identical for every world size; collective), ``"use4"``
+        :meth:`specific_risk_use4` (EW Newey-West vol, shrunk, times the specific
+        volatility-regime multiplier; collective); None ignores specific risk.  Returns :class:`ops.attribution.RiskAttribution`.
         """
         from ..ops import attribution as attr
         if self.stats is None:
@@ -414,7 +478,7 @@ class RiskModel:
             raise RuntimeError(f"covariance series {which!r} not computed yet")
         x = attr.portfolio_exposure(p.styles, p.cap, p.ret, p.ind, h.contiguous(), self.stats, p.P)
         if isinstance(specific_vol, str):
-            specific_vol = self.specific_risk_shrunk()
+            specific_vol = self._specific_vol_named(specific_vol)
         svar = None if specific_vol is None else attr.portfolio_specific_var(h, specific_vol)
         return attr.risk_attribution(x, cov, svar)
 
@@ -428,9 +492,9 @@ class RiskModel:
             raise RuntimeError(f"covariance series {which!r} not computed yet")
         if specific_vol is None:
             raise ValueError("the asset covariance needs specific volatilities: pass a tensor "
-                             "[N] / [D_loc, N] or 'shrunk'")
+                             "[N] / [D_loc, N], 'shrunk' or 'use4'")
         if isinstance(specific_vol, str):
-            specific_vol = self.specific_risk_shrunk()
+            specific_vol = self._specific_vol_named(specific_vol)
         return cov, specific_vol.to(self.device)
 
     def _rows(self, h: torch.Tensor) -> torch.Tensor:

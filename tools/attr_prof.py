@@ -3,7 +3,12 @@ sub-step of RiskModel.risk_attribution timed with HIP events (median of 5).
 
 ``--bayes-shrink [CALLS]``: only ``bayes_shrink`` (the cap-decile shrink kernel of
 csrc/xs_reduce.hip) on the stage's own inputs, median / min / max of CALLS (7) calls after a
-warm-up."""
+warm-up.
+
+``--specific-risk``: the specific-risk model (csrc/specific_risk.hip): ``ewnw_vol`` at window
+252 with 0 and 5 lags, ``spec_bias2`` and the whole ``specific_risk_use4`` call, next to two
+baselines of the same run: the ``trailing_vol`` kernel and the EW Newey-West algebra written
+with torch ops on the GPU (median / min / max of 7 calls after a warm-up)."""
 import json
 import os
 import statistics
@@ -49,6 +54,31 @@ if "--bayes-shrink" in sys.argv:
     i = sys.argv.index("--bayes-shrink")
     calls = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 7
     print(json.dumps({"bayes_shrink": t(lambda: bayes_shrink(vol, p.cap.double(), 10, 1.0), calls, True)}))
+    sys.exit(0)
+if "--specific-risk" in sys.argv:
+    from llm_driven_multi_factor_model_amd.ops import specific_risk as sr
+
+    def ewnw_torch(lags, W=252, hl=84.0):
+        """The two-pass algebra of ops/specific_risk.py with torch ops on the device."""
+        return sr._ewnw_vol_cpu(halo, e, W, sr.ew_weights(W, hl).tolist(), lags, 1)
+
+    sig = m.specific_risk_use4()
+    cap = p.cap
+    v5 = sr.ewnw_vol(halo, e, 252, 84.0, 5)
+    err = ((ewnw_torch(5) - v5).abs() / v5.abs().clamp(min=1e-300))
+    res = {
+        "shape": [p.D, p.N], "window": 252, "half_life": 84.0,
+        "trailing_vol": t(lambda: attr.trailing_vol(halo, e, 252, 1), 7, True),
+        "ewnw_vol_lags0": t(lambda: sr.ewnw_vol(halo, e, 252, 84.0, 0), 7, True),
+        "ewnw_vol_lags5": t(lambda: sr.ewnw_vol(halo, e, 252, 84.0, 5), 7, True),
+        "ewnw_torch_lags0": t(lambda: ewnw_torch(0), 3, True),
+        "ewnw_torch_lags5": t(lambda: ewnw_torch(5), 3, True),
+        "ewnw_torch_vs_kernel_max_rel": float(torch.nan_to_num(err, nan=0.0).max()),
+        "spec_bias2": t(lambda: sr.spec_bias2(e, sig, cap), 7, True),
+        "specific_risk_use4": t(lambda: m.specific_risk_use4(), 7, True),
+        "specific_risk_shrunk": t(lambda: m.specific_risk_shrunk(), 7, True),
+    }
+    print(json.dumps(res))
     sys.exit(0)
 H = h[None, :].expand(p.D, -1).contiguous()
 sv = m.specific_risk_shrunk()

@@ -4,7 +4,8 @@
     python -m llm_driven_multi_factor_model_amd.cli risk   --data data/barra_data_csi.csv \
         --industry data/industry_info.csv --out results/ [--preset reference] [--sims 100] \
         [--checkpoint risk.ckpt] [--resume risk.ckpt] [--attribution equal] [--mongo-uri URI] \
-        [--specific-model use4] [--time-scan carry] [--no-deterministic] [--bias-stat 21 --bias-start 1000]
+        [--specific-model use4] [--time-scan carry] [--no-deterministic] [--bias-stat 21 --bias-start 1000] \
+        [--bias-test portfolios.csv]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m llm_driven_multi_factor_model_amd.cli risk ...
     python -m llm_driven_multi_factor_model_amd.cli factors --prices prices.csv --index index.csv \
         --industry sw_industry.csv --out data/
@@ -117,6 +118,9 @@ def cmd_risk(a):
                                                        a.specific_model)
     if a.bias_stat is not None:
         paths["eigenfactor_bias"] = _write_bias_stat(model, a.bias_stat, a.bias_start, a.out, ctx)
+    if a.bias_test:
+        paths["bias_test"] = _write_bias_test(model, a.bias_test, a.out, ctx, a.specific_model,
+                                              a.bias_test_window)
     if ctx.rank == 0:
         log.info("stage ms: %s", json.dumps({k: round(v, 3) for k, v in model.times.ms.items()}))
         for k, v in paths.items():
@@ -152,6 +156,45 @@ def _write_attribution(model, spec: str, out_dir: str, ctx, specific_model: str 
     if ctx.rank == 0:
         df = pd.DataFrame({k: v.cpu().numpy() for k, v in got.items()},
                           index=pd.DatetimeIndex(dates, name="date"))
+        os.makedirs(out_dir, exist_ok=True)
+        df.to_csv(path)
+    return path
+
+
+def _write_bias_test(model, spec: str, out_dir: str, ctx, specific_model: str = "trailing",
+                     window: int = 252):
+    """Portfolio bias test (``RiskModel.bias_test``, out of sample, VRA covariance) of the test
+    portfolios of ``spec``: "equal" or a CSV with ``stocknames`` plus one weight column per
+    portfolio (held on every date).  Collective; rank 0 writes ``bias_test.csv``, one row per
+    portfolio: bias, n_obs, q_stat, mean |rolling bias - 1| and mean coverage."""
+    from .parallel import dist as pdist
+    N = model.panel.N
+    if spec == "equal":
+        names, H = ["equal"], torch.full((1, N), 1.0 / N, dtype=torch.float64)
+    else:
+        w = pd.read_csv(spec)
+        names = [c for c in w.columns if c != "stocknames"]
+        pos = {str(s): i for i, s in enumerate(model.panel.stocks)}
+        rows = [(pos[s], k) for k, s in enumerate(w["stocknames"].astype(str)) if s in pos]
+        H = torch.zeros(len(names), N, dtype=torch.float64)
+        vals = torch.from_numpy(w[names].to_numpy(dtype=np.float64))
+        H[:, [i for i, _ in rows]] = vals[[k for _, k in rows]].T
+    r = model.bias_test(H.to(model.device),
+                        specific_vol="use4" if specific_model == "use4" else "shrunk",
+                        window=window, min_periods=max(1, min(63, window // 4)))
+    got = {k: pdist.gather_to_root(v.contiguous(), ctx)
+           for k, v in (("rb", r.stats.rolling_bias), ("cov", r.coverage))}
+    path = os.path.join(out_dir, "bias_test.csv")
+    if ctx.rank == 0:
+        def colmean(x):
+            ok = torch.isfinite(x)
+            return (torch.where(ok, x, torch.zeros_like(x)).sum(0) / ok.sum(0)).cpu().numpy()
+        df = pd.DataFrame({"bias": r.stats.bias.cpu().numpy(),
+                           "n_obs": r.stats.n_obs.cpu().numpy(),
+                           "q_stat": r.stats.q_stat.cpu().numpy(),
+                           "mrad": colmean((got["rb"] - 1.0).abs()),
+                           "coverage": colmean(got["cov"])},
+                          index=pd.Index(names, name="portfolio"))
         os.makedirs(out_dir, exist_ok=True)
         df.to_csv(path)
     return path
@@ -302,6 +345,12 @@ def main(argv=None):
     r.add_argument("--specific-model", choices=["trailing", "use4"], default="trailing",
                    help="specific risk behind --attribution: shrunk trailing vol, or the EW "
                         "Newey-West vol with the specific volatility-regime multiplier")
+    r.add_argument("--bias-test", default=None,
+                   help="'equal' or a CSV (stocknames, one weight column per portfolio): write "
+                        "bias_test.csv (out-of-sample portfolio bias test; honours "
+                        "--specific-model)")
+    r.add_argument("--bias-test-window", type=int, default=252,
+                   help="window of the rolling bias statistic behind bias_test.csv")
     r.add_argument("--device", default=None, help="cpu to force the CPU path")
     r.add_argument("--long-specific", action="store_true")
     r.add_argument("--checkpoint", default=None, help="write a resumable checkpoint here")

@@ -593,6 +593,57 @@ class RiskModel:
         beta = Sh / (hz * Sh).sum(-1, keepdim=True)
         return torch.where(m, beta, torch.full_like(beta, float("nan")))
 
+    # --------------------------------------------------------------- model validation
+    def bias_test(self, h: torch.Tensor, which: str = "vra",
+                  specific_vol: torch.Tensor | str = "shrunk", per_date: bool = False,
+                  out_of_sample: bool = True, universe: torch.Tensor | None = None,
+                  window: int = 252, min_periods: int = 63, start: int = 0):
+        """Portfolio bias test (:mod:`ops.bias_test`) of the chosen covariance series and
+        specific-risk model on test portfolios ``h``: [N] or [B, N] held on every date, with
+        ``per_date`` [D_loc, N] or [D_loc, B, N].  ``which`` / ``specific_vol`` / ``universe`` as
+        in :meth:`min_variance`.
+
+        ``out_of_sample`` (default): row t is tested with the forecast made at t - 1, ``cov[t -
+        1]`` and the specific volatility of t - 1, against the exposures ``X_t`` and the return
+        ``ret[t]`` that follows them (``cov[t]`` and the specific volatility of row t already
+        contain that return): the alignment of :meth:`specific_risk_use4`.  The first global
+        date of a run has no forecast; its z is NaN.  Otherwise row t's own forecasts are used
+        (a diagnostic).
+
+        Returns :class:`ops.bias_test.BiasTest`: ``z``, ``forecast_vol``, ``realised`` and
+        ``coverage`` (= held / gross weight) [D_loc, B], and the statistics of z over the global
+        dates >= ``start``: ``bias``, ``n_obs``, ``q_stat`` and ``mrad_mean`` come from the
+        all-gathered z rows and are the same on every rank and for every world size,
+        ``rolling_bias`` / ``mrad`` cover this rank's dates (windows cross rank boundaries
+        through a halo).  Collectives: the two forecast halos, the z halo, the z gather, and
+        what the named ``specific_vol`` makes."""
+        from ..ops import bias_test as bt
+        cov, sv = self._cov_inputs(which, specific_vol)
+        p = self.panel
+        D, K = p.D, self.K
+        s = sv.to(torch.float64)
+        s = (s[None, :].expand(D, -1) if s.dim() == 1 else s).contiguous()
+        F = cov.to(torch.float64)
+        if out_of_sample:
+            Ff = F.reshape(D, K * K).contiguous()
+            F = torch.cat([pdist.halo_prev_rows(Ff, 1, self.ctx, self.sizes), Ff])[:D]
+            F = F.reshape(D, K, K)
+            s = torch.cat([pdist.halo_prev_rows(s, 1, self.ctx, self.sizes), s])[:D]
+        fc = bt.portfolio_forecast(p.styles, p.cap, p.ret, p.ind, self.stats, p.P,
+                                   h.to(self.device), F, s, per_date=per_date, universe=universe)
+        z = bt.standardised(fc)
+        var = fc.factor_var + fc.specific_var
+        nan = torch.full_like(var, float("nan"))
+        vol = torch.sqrt(torch.where(torch.isfinite(var) & (var > 0), var, nan))
+        # the statistics see the global dates >= start only
+        t = self.t_lo + torch.arange(D, device=z.device)
+        zs = torch.where((t >= start)[:, None], z, nan).contiguous()
+        halo = pdist.halo_prev_rows(zs, window - 1, self.ctx, self.sizes)
+        zg = pdist.all_gather_rows(zs, self.ctx, self.sizes)
+        st = bt.bias_stats(zs, halo, zg, window, min_periods)
+        return bt.BiasTest(z=z, forecast_vol=vol, realised=fc.realised,
+                           coverage=fc.held / fc.gross, stats=st)
+
     # --------------------------------------------------------------- pandas views
     def factor_returns_frame(self):
         import pandas as pd

@@ -5,7 +5,7 @@
         --industry data/industry_info.csv --out results/ [--preset reference] [--sims 100] \
         [--checkpoint risk.ckpt] [--resume risk.ckpt] [--attribution equal] [--mongo-uri URI] \
         [--specific-model use4] [--time-scan carry] [--no-deterministic] [--bias-stat 21 --bias-start 1000] \
-        [--bias-test portfolios.csv]
+        [--bias-test portfolios.csv] [--factor-stats]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m llm_driven_multi_factor_model_amd.cli risk ...
     python -m llm_driven_multi_factor_model_amd.cli factors --prices prices.csv --index index.csv \
         --industry sw_industry.csv --out data/
@@ -121,6 +121,8 @@ def cmd_risk(a):
     if a.bias_test:
         paths["bias_test"] = _write_bias_test(model, a.bias_test, a.out, ctx, a.specific_model,
                                               a.bias_test_window)
+    if a.factor_stats:
+        paths.update(_write_factor_stats(model, a.out, ctx))
     if ctx.rank == 0:
         log.info("stage ms: %s", json.dumps({k: round(v, 3) for k, v in model.times.ms.items()}))
         for k, v in paths.items():
@@ -198,6 +200,37 @@ def _write_bias_test(model, spec: str, out_dir: str, ctx, specific_model: str = 
         os.makedirs(out_dir, exist_ok=True)
         df.to_csv(path)
     return path
+
+
+def _write_factor_stats(model, out_dir: str, ctx):
+    """Standard errors and t-statistics of the factor returns (``RiskModel.factor_tstats``).
+    Collective (one gather per column); rank 0 writes ``factor_tstats.csv``, one row per (date,
+    factor): f, se, t; and ``factor_significance.csv``, one row per factor: the mean |t| and the
+    share of dates with |t| > 2, over the dates with a finite t (``n_obs``)."""
+    from .parallel import dist as pdist
+    st = model.factor_tstats()
+    got = {k: pdist.gather_to_root(v.contiguous(), ctx)
+           for k, v in (("f", model.factor_ret), ("se", st.se), ("t", st.t))}
+    dates = model._global_dates()
+    paths = {"factor_tstats": os.path.join(out_dir, "factor_tstats.csv"),
+             "factor_significance": os.path.join(out_dir, "factor_significance.csv")}
+    if ctx.rank == 0:
+        names = list(model.panel.factor_names)
+        T, K = got["t"].shape
+        idx = pd.DatetimeIndex(dates).strftime("%Y-%m-%d")
+        df = pd.DataFrame({"date": np.repeat(idx.values, K), "factor": np.tile(names, T),
+                           **{k: v.cpu().numpy().reshape(-1) for k, v in got.items()}})
+        os.makedirs(out_dir, exist_ok=True)
+        df.to_csv(paths["factor_tstats"], index=False)
+        t = got["t"].cpu().abs()
+        ok = torch.isfinite(t)
+        n = ok.sum(0)
+        zero = torch.zeros((), dtype=t.dtype)
+        sig = pd.DataFrame({"mean_abs_t": (torch.where(ok, t, zero).sum(0) / n).numpy(),
+                            "share_abs_t_gt_2": ((ok & (t > 2)).sum(0) / n).numpy(),
+                            "n_obs": n.numpy()}, index=pd.Index(names, name="factor"))
+        sig.to_csv(paths["factor_significance"])
+    return paths
 
 
 def _write_bias_stat(model, predlen: int, start: int, out_dir: str, ctx):
@@ -351,6 +384,10 @@ def main(argv=None):
                         "--specific-model)")
     r.add_argument("--bias-test-window", type=int, default=252,
                    help="window of the rolling bias statistic behind bias_test.csv")
+    r.add_argument("--factor-stats", action="store_true",
+                   help="write factor_tstats.csv (date, factor, f, se, t) and "
+                        "factor_significance.csv (per factor: mean |t|, share of dates with "
+                        "|t| > 2)")
     r.add_argument("--device", default=None, help="cpu to force the CPU path")
     r.add_argument("--long-specific", action="store_true")
     r.add_argument("--checkpoint", default=None, help="write a resumable checkpoint here")

@@ -83,6 +83,7 @@ class RiskModel:
         self.B2_global = self.B2 = None
         self.nw_params = None     # (q, tau) of the last newey_west() call
         self.spec_vra_lambda = None   # [D_loc], set by specific_risk_use4()
+        self._est_cov = None          # (stats it was formed from, EstCov), set by estimator_cov()
 
     def _stage(self, name: str):
         return trace.stage(name, self.times, self.device, sync=self.sync_stages,
@@ -643,6 +644,59 @@ class RiskModel:
         st = bt.bias_stats(zs, halo, zg, window, min_periods)
         return bt.BiasTest(z=z, forecast_vol=vol, realised=fc.realised,
                            coverage=fc.held / fc.gross, stats=st)
+
+    # --------------------------------------------------------------- the regression as an estimator
+    def _panel_args(self):
+        if self.stats is None:
+            raise RuntimeError("run regress() first")
+        p = self.panel
+        return p.styles, p.cap, p.ret, p.ind, self.stats, p.P
+
+    def estimator_cov(self):
+        """:class:`ops.pure_factor.EstCov` of this rank's dates: the estimator covariance ``C``
+        [D_loc, K, K] of the regression (``Var(f_d) = sigma_d^2 C_d``, ``Omega_d = C_d X_d^T
+        W_d``), the ``rank`` the pseudo-inverse kept and the stock count ``n``, with
+        ``config.pivot_mode``.  Per date: no collective.  Kept for the two methods below until
+        :meth:`regress` runs again."""
+        from ..ops import pure_factor as pf
+        args = self._panel_args()
+        if self._est_cov is None or self._est_cov[0] is not self.stats:
+            self._est_cov = (self.stats, pf.estimator_cov(*args, pivot_mode=self.cfg.pivot_mode))
+        return self._est_cov[1]
+
+    def factor_tstats(self):
+        """:class:`ops.pure_factor.FactorStats` of this rank's dates: standard errors ``se`` and
+        t-statistics ``t`` [D_loc, K] of the factor returns, the residual variance ``sigma2`` and
+        the degrees of freedom ``dof`` [D_loc].  Needs the specific returns of ``regress()``.
+        Per date: no collective."""
+        from ..ops import pure_factor as pf
+        args = self._panel_args()
+        if self.specific_ret is None:
+            raise RuntimeError("factor_tstats needs specific returns: regress(want_resid=True)")
+        return pf.factor_return_stats(*args, self.factor_ret, self.specific_ret,
+                                      self.estimator_cov())
+
+    def pure_factor_portfolios(self, factors=None) -> torch.Tensor:
+        """Pure factor portfolios ``Omega`` [D_loc, S, N] float64 of the selected factors: row j
+        of date d holds the stock weights whose return on date d is the factor return
+        ``f[d, sel_j]`` (unit exposure to that factor, none to the others).  ``factors``: an index
+        list into the K factors, or ``"country"``, ``"industries"``, ``"styles"``, ``"all"`` /
+        None.  The output feeds :meth:`bias_test` as ``bias_test(H, per_date=True)``, the USE4
+        test of the model on its own factor portfolios.  Per date: no collective.
+
+        Memory: ``D_loc S N 8`` bytes; an all-factor call at 2520 dates x 5000 stocks x K = 42 is
+        4.2 GB, the ten styles alone 1.0 GB."""
+        from ..ops import pure_factor as pf
+        args = self._panel_args()
+        P, K = self.panel.P, self.K
+        if isinstance(factors, str):
+            named = {"country": [0], "industries": list(range(1, 1 + P)),
+                     "styles": list(range(1 + P, K)), "all": None}
+            if factors not in named:
+                raise ValueError(f"factors must be an index list or one of {sorted(named)}, got "
+                                 f"{factors!r}")
+            factors = named[factors]
+        return pf.pure_factor_weights(*args, self.estimator_cov().C, factors)
 
     # --------------------------------------------------------------- pandas views
     def factor_returns_frame(self):

@@ -45,6 +45,18 @@ __device__ __forceinline__ void dir_stage(const float* __restrict__ x, int R, in
   }
 }
 
+// A regressor that is exactly constant over the window, x = c: Sxx / Sw and mx^2 are both
+// c^2 (1 + d) with |d| <= (m + 2) eps for sums over m rows (one rounding per fma and per added
+// weight, the two divisions, the square), so vxx = Sxx / Sw - mx^2 is rounding noise of either
+// sign, |vxx| <= 3 (m + 2) eps Sxx / Sw, and cxy / vxx noise over noise.  Such a window (vxx
+// within 4 (m + 2) eps of Sxx / Sw; a regressor that genuinely varies that little has lost its
+// slope to the same rounding) takes the reference's minimum-norm (pinv) solution of the
+// rank-1 system: (a, b) = my / (1 + c^2) (1, c), residuals y - my.  m = the window's valid rows
+// in the direct kernel, the <= 512 rows a prefix spans in the segment kernel.
+__device__ __forceinline__ bool beta_degenerate(double vxx, double sxx, int m) {
+  return !(vxx > 4.0 * (double)(m + 2) * 2.220446049250313e-16 * sxx);
+}
+
 __global__ __launch_bounds__(256) void beta_hsigma_kernel(const float* __restrict__ y,
                                                           const float* __restrict__ x,
                                                           const int* __restrict__ seg_lo, int R,
@@ -83,14 +95,16 @@ __global__ __launch_bounds__(256) void beta_hsigma_kernel(const float* __restric
     const double mx = Sx / Sw, my = Sy / Sw;
     const double vxx = Sxx / Sw - mx * mx;
     const double cxy = Sxy / Sw - mx * my;
-    const double bb = cxy / vxx;
-    const double aa = my - bb * mx;
+    const bool deg = beta_degenerate(vxx, Sxx / Sw, n);
+    const double bb = deg ? mx * my / (1.0 + mx * mx) : cxy / vxx;
+    const double br = deg ? 0.0 : bb;  // a constant regressor: the residuals about my
+    const double aa = my - br * mx;
     // residual sum of squares: second pass (exact, no cancellation)
     double ssr = 0.0, ww = 1.0;
     for (int j = r; j >= lo; --j) {
       const float yv = Y(j), xv = X(j);
       if (!(fin(yv) && fin(xv))) continue;
-      const double e = (double)yv - aa - bb * (double)xv;
+      const double e = (double)yv - aa - br * (double)xv;
       ssr = fma(ww * e, e, ssr);
       ww *= lam;
     }
@@ -385,20 +399,26 @@ struct BetaOp {  // y ~ 1 + x (ret ~ mret): sums of 1, x, y, xx, xy, yy
   // ew_window_san_kernel: the weight sum of a window is implied by its valid count n
   // (sum_(k<n) lam^k, a table), so only the 5 data sums x, y, xx, xy, yy are carried
   static constexpr int NSX = 5;
+  static constexpr int SC = 2;  // the sum whose anchored prefix scales emit_x's rounding noise
   __device__ static void vals_x(float yv, float xv, double (&v)[NSX]) {
     const double x = xv, y = yv;
     v[0] = x; v[1] = y; v[2] = x * x; v[3] = x * y; v[4] = y * y;
   }
+  // pxx: the row's anchored prefix of xx (>= the window's S[2]: the same weights over more
+  // rows).  S[2] is a difference of two such prefixes, so its rounding noise scales with pxx,
+  // not with S[2] itself: a window of exact zeros behind non-zero rows leaves S[2] = +-noise.
   __device__ static void emit_x(const double (&S)[NSX], double iw, int n, int minp, int r,
-                                float* o0, float* o1) {
+                                float* o0, float* o1, double pxx) {
     float b = qnanf(), h = qnanf();
     if (n >= minp && n > 2) {
       const double mx = S[0] * iw, my = S[1] * iw;
       const double vxx = S[2] * iw - mx * mx;
       const double cxy = S[3] * iw - mx * my;
-      const double bb = cxy * frcp(vxx);
+      const bool deg = beta_degenerate(vxx, pxx * iw, 512);
+      const double bb = deg ? mx * my * frcp(fma(mx, mx, 1.0)) : cxy * frcp(vxx);
       // Sw (vyy - b cxy) with Sw vyy = Syy - Sy my and Sw cxy = Sxy - Sx my
-      const double ssr = fmax((S[4] - S[1] * my) - bb * (S[3] - S[0] * my), 0.0);
+      const double ssr =
+          fmax((S[4] - S[1] * my) - (deg ? 0.0 : bb * (S[3] - S[0] * my)), 0.0);
       b = (float)bb;
       h = __builtin_amdgcn_sqrtf((float)ssr * __builtin_amdgcn_rcpf((float)(n - 2)));
     }
@@ -409,12 +429,13 @@ struct BetaOp {  // y ~ 1 + x (ret ~ mret): sums of 1, x, y, xx, xy, yy
 
 struct DastdOp {  // e = ret - mret: sums of 1, e, ee; weighted population std
   static constexpr int NSX = 2;  // ew_window_san_kernel: the weight sum comes from the count
+  static constexpr int SC = 1;
   __device__ static void vals_x(float a, float bm, double (&v)[NSX]) {
     const double e = (double)a - (double)bm;
     v[0] = e; v[1] = e * e;
   }
   __device__ static void emit_x(const double (&S)[NSX], double iw, int n, int minp, int r,
-                                float* o0, float*) {
+                                float* o0, float*, double) {
     float o = qnanf();
     if (n >= minp) {
       const double m = S[0] * iw;
@@ -624,7 +645,7 @@ __global__ __launch_bounds__(kEwNT) __attribute__((amdgpu_waves_per_eu(4))) void
         row(sa[q], sb[q], sd[q], L, cl);
       }
       // the window sum of row p0 - 1, then per row S <- f S + v_r - lam^nv v_(r-W)
-      double S[NS];
+      double S[NS], en = E[Op::SC];  // en: the anchored prefix of sum SC, carried per row
       {
         const unsigned dp = sd[ew_idx<C>(p0 - 1)];
         const bool in = (int)(dp & kCdD) >= W;
@@ -637,6 +658,12 @@ __global__ __launch_bounds__(kEwNT) __attribute__((amdgpu_waves_per_eu(4))) void
         const int r = g0 + p0 + i;
         if (rd[i] & 0x8000u) break;  // past the end of the panel
         row(ra[i], rb[i], rd[i], S, ce);
+        {
+          const bool st = (rd[i] & kCdD) == 0u, ok = (rd[i] & kCdOk) != 0u;
+          double vr[NS];
+          Op::vals_x(ra[i], rb[i], vr);
+          en = fma(st ? 0.0 : (ok ? lam : 1.0), en, vr[Op::SC]);
+        }
         const int q = ew_idx<C>(lp + i);
         const unsigned cq = sd[q];
         const bool stq = (cq & kCdD) == 0u, okq = (cq & kCdOk) != 0u;
@@ -649,7 +676,7 @@ __global__ __launch_bounds__(kEwNT) __attribute__((amdgpu_waves_per_eu(4))) void
 #pragma unroll
         for (int k = 0; k < NS; ++k) S[k] = fma(-w, vq[k], S[k]);
         const int ro = omap[r];
-        if (ro >= 0) Op::emit_x(S, isw[nv], nv, minp, ro, o0, o1);
+        if (ro >= 0) Op::emit_x(S, isw[nv], nv, minp, ro, o0, o1, en);
       }
     }
     __syncthreads();  // LDS tile / carries are rewritten by the next iteration
@@ -691,8 +718,10 @@ void launch_ew_seg(const float* a, const float* b, const int* seg_v, const int* 
 // S_j(m) = T_j + lam^64 T_(j+1) + ... + lam^(64 (m-1)) T_(j+m-1) (T = segment totals) -- a
 // left-fold table of <= 9 entries per segment built once per tile, so a row costs one fma and a
 // handful of LDS reads whatever its window spans (the RSTR ratio's common factor lam^(kl - 64 jl)
-// cancels).  A 256-thread block stages 2048 output rows plus an H-row halo (H >= the reach
-// W + L - 1 rounded up to 64), every row loaded once and scanned per 64-row segment.
+// cancels; ops/rolling.py keeps decays with lam^63 < 2^-20 off this kernel, where the rows of
+// G_jl before the window would outweigh it).  A 256-thread block stages 2048 output rows plus
+// an H-row halo (H >= the reach W + L - 1 rounded up to 64), every row loaded once and scanned
+// per 64-row segment.
 constexpr int kPosOut = 2048;
 constexpr int kPosMF = 9;  // fold-table entries per segment: m = 0 .. 8 (reach <= 512)
 
@@ -710,6 +739,11 @@ __global__ __launch_bounds__(256) void poswin_seg_kernel(
   __shared__ int tc[NSEG];
   __shared__ double fn[NSEG][kPosMF], fd[RATIO ? NSEG : 1][kPosMF];
   __shared__ int fc[NSEG][kPosMF];
+  // The sums: which rows of each segment are finite and non-zero (one ballot per segment), and
+  // their count in bits 16.. of tc / fc beside the valid count (both <= 576).  A window holding
+  // none sums to exactly 0 -- decided on these counts, not on the difference of two prefix sums
+  // whose lanes associated the rows before the window differently.
+  __shared__ unsigned long long gz[RATIO ? 1 : NSEG];
   __shared__ double lpm[kPosMF];  // lam^(64 m)
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int g0 = blockIdx.x * kPosOut - H;
@@ -737,10 +771,13 @@ __global__ __launch_bounds__(256) void poswin_seg_kernel(
     }
     const int c = __popcll(__ballot(ok) & below);
     gc[s * 64 + lane] = (unsigned char)c;
+    unsigned long long nz = 0;
+    if constexpr (!RATIO) nz = __ballot(xv != 0.0);
     if (lane == 63) {
       tn[s] = Gn;
       td[s] = Gd;
-      tc[s] = c;
+      tc[s] = c | (__popcll(nz) << 16);
+      if constexpr (!RATIO) gz[s] = nz;
     }
   }
   if (threadIdx.x == 0) {
@@ -787,13 +824,18 @@ __global__ __launch_bounds__(256) void poswin_seg_kernel(
         const double f = lpm[m];
         double an = fma(f, gn[tr], fn[jl][m]);
         if (mid) an -= gn[tl - 1];
-        int c = fc[jl][m] + gc[tr] - (mid ? gc[tl - 1] : 0);
+        const int fcv = fc[jl][m];
+        const int c = (fcv & 0xFFFF) + gc[tr] - (mid ? gc[tl - 1] : 0);
         if (c >= mp) {
           if constexpr (RATIO) {
             double ad = fma(f, gd[tr], fd[jl][m]);
             if (mid) ad -= gd[tl - 1];
             res = (float)(an * frcp(ad));
           } else {
+            // finite non-zero rows of the window, by the same decomposition as its count
+            const int z = (fcv >> 16) + __popcll(gz[jl + m] & (~0ull >> (63 - (tr & 63)))) -
+                          (mid ? __popcll(gz[jl] & (~0ull >> (64 - (tl & 63)))) : 0);
+            if (z == 0) an = 0.0;
             res = log_out ? (an == 0.0 ? qnanf() : (float)log(an)) : (float)an;
           }
         }

@@ -46,6 +46,18 @@ POS_SEG = 64       # RSTR / window sums / CMRA anchor segments (the window's fir
 EW_MAX_W = 256     # segment kernels' window limits; larger windows take the direct kernels
 POS_MAX_REACH = 512
 CMRA_MIN_W, CMRA_MAX_W = 65, 257
+# The segment RSTR differences two weighted prefixes anchored up to POS_SEG - 1 rows before the
+# window, whose leading rows outweigh the window's by lam^-(POS_SEG - 1): that many of the 53
+# fp64 bits cancel.  An fp32 output over <= 2^9 summed rows keeps 20 to spare; a faster decay
+# (half-life under ~3.2 rows) takes the direct kernel, which weighs from the window's own start.
+POS_MIN_DECAY = 2.0 ** -20
+
+
+def rstr_seg_ok(window: int, lag: int, lam: float) -> bool:
+    """Whether RSTR over ``window`` rows lagged ``lag`` with decay ``lam`` runs on the segment
+    kernel (else the direct one)."""
+    return (window >= 1 and lag >= 0 and window + lag - 1 <= POS_MAX_REACH
+            and lam ** (POS_SEG - 1) >= POS_MIN_DECAY)
 
 
 def ew_reach(window: int) -> int:
@@ -273,6 +285,8 @@ def beta_hsigma(ret, mret, seg_lo, window=252, half_life=63.0, min_periods=42, r
         w = wfull[-n:]
         X = np.column_stack([np.ones(n), xx[ok]])
         sw = np.sqrt(w)
+        # a constant regressor: lstsq returns the minimum-norm solution of the rank-1 system,
+        # like the reference's pinv (the kernels' closed form: csrc/rolling.hip beta_degenerate)
         coef, *_ = np.linalg.lstsq(X * sw[:, None], yy[ok] * sw, rcond=None)
         e = yy[ok] - X @ coef
         b[r] = coef[1]
@@ -282,12 +296,13 @@ def beta_hsigma(ret, mret, seg_lo, window=252, half_life=63.0, min_periods=42, r
 
 # ---------------------------------------------------------------- RSTR
 def rstr(log_ret, seg_lo, T=504, L=21, half_life=126.0, min_periods=42, row_ord=None):
-    """GPU: the segment-anchored positional-window kernel (reach T - 1 <= 512) on the segment
-    layout of ``row_ord`` (see :func:`beta_hsigma`), else the direct kernel."""
+    """GPU: the segment-anchored positional-window kernel (reach T - 1 <= 512 and a decay it
+    resolves, :func:`rstr_seg_ok`) on the segment layout of ``row_ord`` (see
+    :func:`beta_hsigma`), else the direct kernel."""
     R = log_ret.numel()
     W = T - L
     lam = 0.5 ** (1.0 / half_life)
-    if _seg_path(log_ret) and W >= 1 and L >= 0 and W + L - 1 <= POS_MAX_REACH:
+    if _seg_path(log_ret) and rstr_seg_ok(W, L, lam):
         lay = _layout(seg_lo, row_ord, (log_ret,))
         out = torch.empty(R, dtype=torch.float32, device=log_ret.device)
         xv = lay.virt(log_ret)

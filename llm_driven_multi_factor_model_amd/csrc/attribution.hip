@@ -6,12 +6,12 @@
 //   x_country = sum_i h_i,   x_ind[j] = sum_{i in j} h_i,   x_style[q] = sum_i h_i z_iq,
 //   z_iq = (X_iq - mu_q) / sigma   =>   x_style[q] = (sum_i h_i X_iq - mu_q sum_i h_i) / sigma,
 // so the raw panel is read once and never z-scored in memory.  Stocks that are absent or have
-// non-finite inputs (the regression's validity rule) contribute nothing.
+// non-finite inputs (the regression's validity rule, design_row.h) contribute nothing.
 //
 // One 256-thread workgroup per date: fp64 register accumulators for the Q + 1 dense sums, LDS
 // atomics for the industry sums (dynamic LDS), a fixed-order workgroup reduction; style sets
 // wider than 16 run in blocks of 16 styles.
-#include "common.h"
+#include "design_row.h"
 
 namespace {
 
@@ -29,34 +29,24 @@ __global__ __launch_bounds__(256) void portfolio_exposure_kernel(
   extern __shared__ double segs[];
   __shared__ double red[4][QB + 1];
   const int d = blockIdx.x, tid = threadIdx.x;
-  const int Pseg = P > 0 ? P : 1;
+  const DesignDate<T> day(X, cap, ret, ind, d, N, P, Q);
   const bool lead = q0 == 0;
   if (lead)
-    for (int j = tid; j < Pseg; j += blockDim.x) segs[j] = 0.0;
+    for (int j = tid; j < day.Pseg; j += blockDim.x) segs[j] = 0.0;
   __syncthreads();
-  const T* Xd = X + (size_t)d * Q * N;
-  const T* cd = cap + (size_t)d * N;
-  const T* rd = ret + (size_t)d * N;
-  const int16_t* id = ind ? ind + (size_t)d * N : nullptr;
   const double* hd = h + (size_t)d * N;
   double acc[QB + 1];
 #pragma unroll
   for (int q = 0; q <= QB; ++q) acc[q] = 0.0;
   for (int n = tid; n < N; n += blockDim.x) {
-    const T c = cd[n], r = rd[n];
-    const int j = id ? (int)id[n] : 0;
+    T c, r, xf[QB];
+    int j;
+    day.load_base(n, c, r, j);
     const double w = hd[n];
-    bool ok = (j >= 0) && (j < Pseg) && __builtin_isfinite(c) && (c >= T(0)) &&
-              __builtin_isfinite(r) && __builtin_isfinite(w);
-    T xf[QB];
-#pragma unroll
-    for (int q = 0; q < QB; ++q) {
-      xf[q] = q0 + q < Q ? Xd[(size_t)(q0 + q) * N + n] : T(0);
-      ok = ok && __builtin_isfinite(xf[q]);
-    }
+    bool ok = __builtin_isfinite(w) && day.base_ok(c, r, j);
+    day.load_styles_ok(n, xf, ok, q0, Q);
     if (Q > QB)  // styles outside this launch's block still decide validity
-      for (int q = 0; q < Q; ++q)
-        if (q < q0 || q >= q0 + QB) ok = ok && __builtin_isfinite(Xd[(size_t)q * N + n]);
+      day.styles_outside_ok(n, ok, Q, q0, q0 + QB);
     if (!ok || w == 0.0) continue;
     acc[QB] += w;
 #pragma unroll
@@ -84,7 +74,8 @@ __global__ __launch_bounds__(256) void portfolio_exposure_kernel(
     if (tid == 0) o[0] = hs;
     for (int j = tid; j < P; j += blockDim.x) o[1 + j] = segs[j];
   }
-  if (tid < QB && q0 + tid < Q) o[1 + P + q0 + tid] = (red[0][tid] - st[q0 + tid] * hs) * isig;
+  if (tid < QB && q0 + tid < Q)
+    o[1 + P + q0 + tid] = unfold_zscore(red[0][tid], st[q0 + tid], hs, isig);
 }
 
 template <typename T>
@@ -96,24 +87,18 @@ int portfolio_exposure_dispatch(const T* X, const T* cap, const T* ret, const in
   hipStream_t s = (hipStream_t)stream;
   const int K = 1 + P + Q;
   const size_t lds = (size_t)(P > 0 ? P : 1) * sizeof(double);
-  if (Q > 16) {  // wide style sets: blocks of 16 styles, one launch each (the first adds the
-                 // country / industry sums)
-    for (int q0 = 0; q0 < Q; q0 += 16)
-      hipLaunchKernelGGL((portfolio_exposure_kernel<16, T>), dim3(D), dim3(256), lds, s, X, cap,
-                         ret, P > 0 ? ind : nullptr, h, stats, N, P, Q, q0, K, out);
+  if (Q > kMaxQ) {  // wide style sets: blocks of 16 styles, one launch each (the first adds the
+                    // country / industry sums)
+    for (int q0 = 0; q0 < Q; q0 += kMaxQ)
+      hipLaunchKernelGGL((portfolio_exposure_kernel<kMaxQ, T>), dim3(D), dim3(256), lds, s, X,
+                         cap, ret, P > 0 ? ind : nullptr, h, stats, N, P, Q, q0, K, out);
     return (int)hipGetLastError();
   }
-  switch (Q) {
-#define MFA_Q(qq)                                                                              \
-  case qq:                                                                                     \
-    hipLaunchKernelGGL((portfolio_exposure_kernel<qq, T>), dim3(D), dim3(256), lds, s, X, cap, \
-                       ret, P > 0 ? ind : nullptr, h, stats, N, P, Q, 0, K, out);              \
-    break;
-    MFA_Q(1) MFA_Q(2) MFA_Q(3) MFA_Q(4) MFA_Q(5) MFA_Q(6) MFA_Q(7) MFA_Q(8)
-    MFA_Q(9) MFA_Q(10) MFA_Q(11) MFA_Q(12) MFA_Q(13) MFA_Q(14) MFA_Q(15) MFA_Q(16)
-#undef MFA_Q
-  }
-  return (int)hipGetLastError();
+  const bool known = dispatch_q(Q, [&](auto q) {
+    hipLaunchKernelGGL((portfolio_exposure_kernel<decltype(q)::value, T>), dim3(D), dim3(256), lds,
+                       s, X, cap, ret, P > 0 ? ind : nullptr, h, stats, N, P, Q, 0, K, out);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // Point-in-time trailing specific volatility (RiskModel.specific_vol_series): for every stock

@@ -3,7 +3,8 @@
 //
 // X_d is the regression's design matrix [country | one-hot industries | cap-weighted z-scored
 // styles] (K = 1 + P + Q columns); it is never materialised: the kernels stream the raw panel
-// and fold the z-scoring in from stats = (mu_q, sigma, n) of mfa_xs_wls, as attribution.hip does.
+// and fold the z-scoring in from stats = (mu_q, sigma, n) of mfa_xs_wls (design_row.h: the view
+// of a date, the validity rule, the fold and its inverse).
 // With a_n = 1 / s_n^2 on the universe (0 elsewhere) and F = R R^T (R = U sqrt(max(lambda, 0))),
 //   Sigma^-1 b = a o (b - X c),      c = R (I + R^T G R)^-1 R^T g,
 //   G = X^T diag(a) X,               g = X^T (a o b)
@@ -14,15 +15,12 @@
 //   factor_xty_kernel     X^T h for up to 4 h per pass       (g and X^T h; order-fixed sums)
 //   woodbury_coef_kernel  G, eigenpairs of F, g -> c         (K <= 64: M in LDS, Cholesky)
 //   factor_apply_kernel   out = u o rhs + v o (X c)          (all right-hand sides in one pass)
-#include "common.h"
+#include "design_row.h"
 
 namespace {
 
 using namespace mfa;
 
-constexpr int kThreads = 256, kWaves = 4;
-constexpr int kMaxK = 64;     // one-wave tier of the eigen solver (ops.eigen.WIDE_K)
-constexpr int kMaxQ = 16;
 constexpr int kApplyNB = 8;   // right-hand sides per factor_apply launch (c lives in LDS)
 
 // ------------------------------------------------------------------------------- factor Gram
@@ -60,35 +58,27 @@ __device__ __forceinline__ void gram_body(const T* __restrict__ X, const T* __re
                                           double* __restrict__ G, double* lds) {
   constexpr int NT = tri_count(Q, R0, R1), NACC = NT + Q + 1, QS = Q + 1;
   constexpr bool LEAD = R0 == 0;
-  const int d = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int Pseg = P > 0 ? P : 1, K = 1 + P + Q;
+  const int d = blockIdx.x, tid = threadIdx.x, wid = tid >> 6;
+  const DesignDate<T> day(X, cap, ret, ind, d, N, P, Q);
+  const int Pseg = day.Pseg, K = 1 + P + Q;
   double* seg = lds;                              // [kWaves][Pseg][QS]
   double* red = seg + (size_t)kWaves * Pseg * QS;  // [kWaves][NACC]
   double* tot = red + kWaves * gram_nacc_max(Q);   // [NACC]
   if (LEAD && P > 0)
     for (int i = tid; i < kWaves * Pseg * QS; i += kThreads) seg[i] = 0.0;
   __syncthreads();
-  const T* Xd = X + (size_t)d * Q * N;
-  const T* cd = cap + (size_t)d * N;
-  const T* rd = ret + (size_t)d * N;
-  const int16_t* id = ind ? ind + (size_t)d * N : nullptr;
   const double* ad = a + (size_t)d * N;
   double* myseg = seg + (size_t)wid * Pseg * QS;
   double acc[NACC];
 #pragma unroll
   for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
   for (int n = tid; n < N; n += kThreads) {
-    const T c = cd[n], r = rd[n];
-    const int j = id ? (int)id[n] : 0;
+    T c, r, xf[Q];
+    int j;
+    day.load_base(n, c, r, j);
     const double an = ad[n];
-    bool ok = (j >= 0) && (j < Pseg) && __builtin_isfinite(c) && (c >= T(0)) &&
-              __builtin_isfinite(r) && __builtin_isfinite(an) && (an > 0.0);
-    T xf[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      xf[q] = Xd[(size_t)q * N + n];
-      ok = ok && __builtin_isfinite(xf[q]);
-    }
+    bool ok = __builtin_isfinite(an) && (an > 0.0) && day.base_ok(c, r, j);
+    day.load_styles_ok(n, xf, ok);
     if (!ok) continue;
     double x[Q];
 #pragma unroll
@@ -113,21 +103,14 @@ __device__ __forceinline__ void gram_body(const T* __restrict__ X, const T* __re
       atomicAdd(s + Q, an);
     }
   }
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) {
-    const double t = wave_total(acc[i]);
-    if (lane == 0) red[wid * NACC + i] = t;
-  }
+  wave_totals(acc, red);
   __syncthreads();
-  for (int i = tid; i < NACC; i += kThreads)
-    tot[i] = ((red[i] + red[NACC + i]) + red[2 * NACC + i]) + red[3 * NACC + i];
+  for (int i = tid; i < NACC; i += kThreads) tot[i] = sum4(red, NACC, i);
   if (LEAD && P > 0)  // entry i of the four tables is touched by this thread only
-    for (int i = tid; i < Pseg * QS; i += kThreads)
-      seg[i] = ((seg[i] + seg[Pseg * QS + i]) + seg[2 * Pseg * QS + i]) + seg[3 * Pseg * QS + i];
+    for (int i = tid; i < Pseg * QS; i += kThreads) seg[i] = sum4(seg, Pseg * QS, i);
   __syncthreads();
   const double* st = stats + (size_t)d * (Q + 2);
-  bool bad = false;
-  for (int q = 0; q <= Q; ++q) bad = bad || !__builtin_isfinite(st[q]);
+  const bool bad = !stats_finite(st, Q);
   const double isig = 1.0 / st[Q];
   const double S0 = tot[NT + Q];
   double* Gd = G + (size_t)d * K * K;
@@ -146,9 +129,8 @@ __device__ __forceinline__ void gram_body(const T* __restrict__ X, const T* __re
     } else if (r <= P) {  // country / industry x style
       if (!LEAD) continue;
       const int q = c - 1 - P;
-      const double mu = st[q];
-      if (r == 0) v = (tot[NT + q] - mu * S0) * isig;
-      else v = (seg[(r - 1) * QS + q] - mu * seg[(r - 1) * QS + Q]) * isig;
+      if (r == 0) v = unfold_zscore(tot[NT + q], st[q], S0, isig);
+      else v = unfold_zscore(seg[(r - 1) * QS + q], st[q], seg[(r - 1) * QS + Q], isig);
     } else {  // style x style, owned by the part that holds the smaller row
       const int qa = r - 1 - P, qb = c - 1 - P;
       if (qa < R0 || qa >= R1) continue;
@@ -185,25 +167,20 @@ int factor_gram_dispatch(const T* X, const T* cap, const T* ret, const int16_t* 
   if (Q < 1 || Q > kMaxQ || P < 0 || 1 + P + Q > kMaxK || N <= 0) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = gram_lds_doubles(P > 0 ? P : 1, Q) * sizeof(double);
-  switch (Q) {
-#define MFA_Q(qq)                                                                            \
-  case qq:                                                                                   \
-    hipLaunchKernelGGL((factor_gram_kernel<qq, T>), dim3(D, gram_split(qq) == qq ? 1 : 2),   \
-                       dim3(kThreads), lds, s, X, cap, ret, P > 0 ? ind : nullptr, a, stats, \
-                       N, P, G);                                                             \
-    break;
-    MFA_Q(1) MFA_Q(2) MFA_Q(3) MFA_Q(4) MFA_Q(5) MFA_Q(6) MFA_Q(7) MFA_Q(8)
-    MFA_Q(9) MFA_Q(10) MFA_Q(11) MFA_Q(12) MFA_Q(13) MFA_Q(14) MFA_Q(15) MFA_Q(16)
-#undef MFA_Q
-  }
-  return (int)hipGetLastError();
+  const bool known = dispatch_q(Q, [&](auto q) {
+    constexpr int QQ = decltype(q)::value;
+    hipLaunchKernelGGL((factor_gram_kernel<QQ, T>), dim3(D, gram_split(QQ) == QQ ? 1 : 2),
+                       dim3(kThreads), lds, s, X, cap, ret, P > 0 ? ind : nullptr, a, stats, N, P,
+                       G);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // --------------------------------------------------------------------------- X^T h, many h
 // out[d, b, :] = X_d^T h[d, b, :] for nb <= kXtyNB right-hand sides [b0, b0 + nb) of NB in one pass
-// over the panel: the exposures of attribution.hip's portfolio_exposure_kernel (same validity
-// rule: invalid stocks and non-finite h contribute nothing), with the order-fixed reductions of
-// the Gram kernel (one industry table per wave) instead of cross-wave LDS atomics.
+// over the panel: the exposures of attribution.hip's portfolio_exposure_kernel (invalid stocks
+// and non-finite h contribute nothing), with the order-fixed reductions of the Gram kernel (one
+// industry table per wave) instead of cross-wave LDS atomics.
 constexpr int kXtyNB = 4;
 
 __host__ __device__ constexpr size_t xty_lds_doubles(int Pseg, int Q) {
@@ -218,7 +195,7 @@ __global__ __launch_bounds__(kThreads) void factor_xty_kernel(
     double* __restrict__ out) {
   extern __shared__ double xty_lds[];
   constexpr int QS = Q + 1, NACC = kXtyNB * QS;
-  const int d = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int d = blockIdx.x, tid = threadIdx.x, wid = tid >> 6;
   const int Pseg = P > 0 ? P : 1, K = 1 + P + Q;
   double* seg = xty_lds;                                   // [kWaves][kXtyNB][Pseg]
   double* red = seg + (size_t)kWaves * kXtyNB * Pseg;       // [kWaves][NACC]
@@ -226,6 +203,7 @@ __global__ __launch_bounds__(kThreads) void factor_xty_kernel(
   if (P > 0)
     for (int i = tid; i < kWaves * kXtyNB * Pseg; i += kThreads) seg[i] = 0.0;
   __syncthreads();
+  // this kernel keeps its own pointers and style loop; the rule is design_row.h's
   const T* Xd = X + (size_t)d * Q * N;
   const T* cd = cap + (size_t)d * N;
   const T* rd = ret + (size_t)d * N;
@@ -238,8 +216,7 @@ __global__ __launch_bounds__(kThreads) void factor_xty_kernel(
   for (int n = tid; n < N; n += kThreads) {
     const T c = cd[n], r = rd[n];
     const int j = id ? (int)id[n] : 0;
-    bool ok = (j >= 0) && (j < Pseg) && __builtin_isfinite(c) && (c >= T(0)) &&
-              __builtin_isfinite(r);
+    bool ok = design_base_ok(c, r, j, Pseg);
     double x[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
@@ -260,18 +237,11 @@ __global__ __launch_bounds__(kThreads) void factor_xty_kernel(
       }
     }
   }
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) {
-    const double t = wave_total(acc[i]);
-    if (lane == 0) red[wid * NACC + i] = t;
-  }
+  wave_totals(acc, red);
   __syncthreads();
-  for (int i = tid; i < NACC; i += kThreads)
-    tot[i] = ((red[i] + red[NACC + i]) + red[2 * NACC + i]) + red[3 * NACC + i];
+  for (int i = tid; i < NACC; i += kThreads) tot[i] = sum4(red, NACC, i);
   if (P > 0)  // entry i of the four tables is touched by this thread only
-    for (int i = tid; i < kXtyNB * Pseg; i += kThreads)
-      seg[i] = ((seg[i] + seg[kXtyNB * Pseg + i]) + seg[2 * kXtyNB * Pseg + i]) +
-               seg[3 * kXtyNB * Pseg + i];
+    for (int i = tid; i < kXtyNB * Pseg; i += kThreads) seg[i] = sum4(seg, kXtyNB * Pseg, i);
   __syncthreads();
   const double* st = stats + (size_t)d * (Q + 2);
   const double isig = 1.0 / st[Q];
@@ -281,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void factor_xty_kernel(
     double v;
     if (k == 0) v = hs;
     else if (k <= P) v = seg[b * Pseg + k - 1];
-    else v = (tot[b * QS + k - 1 - P] - st[k - 1 - P] * hs) * isig;
+    else v = unfold_zscore(tot[b * QS + k - 1 - P], st[k - 1 - P], hs, isig);
     out[((size_t)d * NB + b0 + b) * K + k] = v;
   }
 }
@@ -296,17 +266,11 @@ int factor_xty_dispatch(const T* X, const T* cap, const T* ret, const int16_t* i
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = xty_lds_doubles(P > 0 ? P : 1, Q) * sizeof(double);
-  switch (Q) {
-#define MFA_Q(qq)                                                                              \
-  case qq:                                                                                     \
-    hipLaunchKernelGGL((factor_xty_kernel<qq, T>), dim3(D), dim3(kThreads), lds, s, X, cap,    \
-                       ret, P > 0 ? ind : nullptr, h, stats, N, P, NB, b0, nb, out);           \
-    break;
-    MFA_Q(1) MFA_Q(2) MFA_Q(3) MFA_Q(4) MFA_Q(5) MFA_Q(6) MFA_Q(7) MFA_Q(8)
-    MFA_Q(9) MFA_Q(10) MFA_Q(11) MFA_Q(12) MFA_Q(13) MFA_Q(14) MFA_Q(15) MFA_Q(16)
-#undef MFA_Q
-  }
-  return (int)hipGetLastError();
+  const bool known = dispatch_q(Q, [&](auto q) {
+    hipLaunchKernelGGL((factor_xty_kernel<decltype(q)::value, T>), dim3(D), dim3(kThreads), lds, s,
+                       X, cap, ret, P > 0 ? ind : nullptr, h, stats, N, P, NB, b0, nb, out);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------ Woodbury inner solve
@@ -416,49 +380,33 @@ __global__ __launch_bounds__(kThreads) void factor_apply_kernel(
   __shared__ double cc[kApplyNB][kMaxK];
   __shared__ int badb[kApplyNB];
   const int d = blockIdx.x, tid = threadIdx.x;
-  const int Pseg = P > 0 ? P : 1, K = 1 + P + Q;
+  const DesignDate<T> day(X, cap, ret, ind, d, N, P, Q);
+  const int K = 1 + P + Q;
   const double* st = stats + (size_t)d * (Q + 2);
   if (tid < nb) {  // one thread per right-hand side: fold (mu, sigma) into c, flag NaN
     const double* cb = c + ((size_t)d * NB + b0 + tid) * K;
-    const double isig = 1.0 / st[Q];
-    bool bad = !__builtin_isfinite(st[Q]);
-    double c0 = cb[0];
-    for (int k = 0; k <= P; ++k) {
-      bad = bad || !__builtin_isfinite(cb[k]);
-      cc[tid][k] = cb[k];
-    }
-    for (int q = 0; q < Q; ++q) {
-      const double cq = cb[1 + P + q] * isig;
-      bad = bad || !__builtin_isfinite(cq) || !__builtin_isfinite(st[q]);
-      cc[tid][1 + P + q] = cq;
-      c0 = fma(-st[q], cq, c0);
-    }
-    cc[tid][0] = c0;
+    fold_zscore(cb, st, P, Q, cc[tid]);
+    // the country coefficient as given, the industry and the folded style coefficients
+    bool bad = !stats_finite(st, Q) || !__builtin_isfinite(cb[0]);
+    for (int k = 1; k < K; ++k) bad = bad || !__builtin_isfinite(cc[tid][k]);
     badb[tid] = bad;
   }
   __syncthreads();
-  const T* Xd = X + (size_t)d * Q * N;
-  const T* cd = cap + (size_t)d * N;
-  const T* rd = ret + (size_t)d * N;
-  const int16_t* id = ind ? ind + (size_t)d * N : nullptr;
   const double* ud = u + (size_t)d * N;
   const double* vd = v + (size_t)d * N;
   const double* rb = rhs + ((size_t)d * NB + b0) * N;
   double* ob = out + ((size_t)d * NB + b0) * N;
   for (int n = tid; n < N; n += kThreads) {
-    const T cp = cd[n], r = rd[n];
-    const int j = id ? (int)id[n] : 0;
+    T cp, r, xf[Q];
+    int j;
+    day.load_base(n, cp, r, j);
     const double un = ud[n], vn = vd[n];
-    bool ok = (j >= 0) && (j < Pseg) && __builtin_isfinite(cp) && (cp >= T(0)) &&
-              __builtin_isfinite(r) && __builtin_isfinite(un) && __builtin_isfinite(vn) &&
-              (vn != 0.0);
+    bool ok = __builtin_isfinite(un) && __builtin_isfinite(vn) && (vn != 0.0) &&
+              day.base_ok(cp, r, j);
+    day.load_styles_ok(n, xf, ok);
     double x[Q];
 #pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const T xf = Xd[(size_t)q * N + n];
-      ok = ok && __builtin_isfinite(xf);
-      x[q] = (double)xf;
-    }
+    for (int q = 0; q < Q; ++q) x[q] = (double)xf[q];
     const int jj = (ok && P > 0) ? 1 + j : 0;
     for (int b = 0; b < nb; ++b) {
       double val = 0.0;
@@ -485,17 +433,12 @@ int factor_apply_dispatch(const T* X, const T* cap, const T* ret, const int16_t*
       b0 + nb > NB)
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  switch (Q) {
-#define MFA_Q(qq)                                                                              \
-  case qq:                                                                                     \
-    hipLaunchKernelGGL((factor_apply_kernel<qq, T>), dim3(D), dim3(kThreads), 0, s, X, cap,    \
-                       ret, P > 0 ? ind : nullptr, u, v, stats, rhs, c, N, P, NB, b0, nb, out); \
-    break;
-    MFA_Q(1) MFA_Q(2) MFA_Q(3) MFA_Q(4) MFA_Q(5) MFA_Q(6) MFA_Q(7) MFA_Q(8)
-    MFA_Q(9) MFA_Q(10) MFA_Q(11) MFA_Q(12) MFA_Q(13) MFA_Q(14) MFA_Q(15) MFA_Q(16)
-#undef MFA_Q
-  }
-  return (int)hipGetLastError();
+  const bool known = dispatch_q(Q, [&](auto q) {
+    hipLaunchKernelGGL((factor_apply_kernel<decltype(q)::value, T>), dim3(D), dim3(kThreads), 0, s,
+                       X, cap, ret, P > 0 ? ind : nullptr, u, v, stats, rhs, c, N, P, NB, b0, nb,
+                       out);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -542,13 +485,7 @@ MFA_API int mfa_woodbury_coef(const double* G, const double* w, const double* U,
   if (D <= 0 || NB <= 0) return 0;
   if (K < 1 || K > kMaxK) return (int)hipErrorInvalidValue;
   const size_t lds = woodbury_lds_bytes(K);
-  static size_t attr = 64 * 1024;  // raise the dynamic-LDS limit once per size
-  if (attr < lds) {
-    if (hipError_t err = hipFuncSetAttribute((const void*)woodbury_coef_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-      return (int)err;
-    attr = lds;
-  }
+  if (hipError_t err = raise_dynamic_lds<woodbury_coef_kernel>(lds)) return (int)err;
   hipLaunchKernelGGL(woodbury_coef_kernel, dim3(D), dim3(kThreads), lds, (hipStream_t)stream, G,
                      w, U, g, NB, K, c);
   return (int)hipGetLastError();

@@ -1,7 +1,7 @@
 // Batched portfolio risk forecasts against realised returns: the sums behind the portfolio bias
 // test (ops/bias_test.py), for every date d and portfolio b in one launch (gfx950).
 //
-// Test set T_d: stocks that pass the regression's validity rule (as factor_xty_kernel), have a
+// Test set T_d: stocks that pass the regression's validity rule (design_row.h), have a
 // finite s_fc[d, n] > 0 and the optional universe[d, n] bit; a position outside T_d, or with a
 // non-finite h, is dropped from every sum, so forecast and realised return describe the same
 // holdings.  Per (d, b), all over T_d:
@@ -16,7 +16,7 @@
 // (one accumulator tile per 16 columns, at most 4 as K <= 64): the column tile is read by all four
 // waves, which is the reuse.  The sums that are not linear in h (h^2 s^2, |h|) and sum h ride in
 // the lane that feeds the A operand; their four per-lane partials (stocks n = i mod 4) are added
-// in a fixed order at the end.  The z-scoring is folded in from stats as factor_xty does, and the
+// in a fixed order at the end.  The z-scoring is folded in from stats (design_row.h), and the
 // K x K quadratic form runs in the epilogue with F_fc[d] in LDS.  Every sum has a fixed order that
 // depends on the stock index alone: the value of (d, b) does not depend on B, on b's row in its
 // tile, on the layout of H or on the other dates of the launch.
@@ -25,7 +25,7 @@
 // one tile of a static H (64 N doubles: L2-resident) and stream different dates of the panel.
 // 16x16x4 f64 layouts (tools/probes/mfma64_probe.hip): A operand lane l = A[l & 15][l >> 4],
 // B operand lane l = B[l >> 4][l & 15], register e of lane l = D[(l >> 4) + 4 e][l & 15].
-#include "common.h"
+#include "design_row.h"
 
 namespace {
 
@@ -33,9 +33,6 @@ using namespace mfa;
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kThreads = 256;
-constexpr int kMaxK = 64;
-constexpr int kMaxQ = 16;
 constexpr int kTile = 64;        // portfolios per workgroup (16 per wave)
 constexpr int kChunk = 64;       // stocks per LDS chunk
 constexpr int kLd = kChunk + 4;  // row stride = 4 mod 32 doubles: the MFMA operand reads of a
@@ -86,17 +83,14 @@ __global__ __launch_bounds__(kThreads) void portfolio_batch_kernel(
   const int d = blockIdx.x, b0 = blockIdx.y * kTile;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int r16 = lane & 15, k4 = lane >> 4;
-  const int Pseg = P > 0 ? P : 1, K = 1 + P + Q, CT = (K + 15) >> 4;
+  const DesignDate<T> day(X, cap, ret, ind, d, N, P, Q);
+  const int K = 1 + P + Q, CT = (K + 15) >> 4;
   double* As = pb_lds;               // [4 waves][16][kLd]: H slices; exposures in the epilogue
   double* Cs = As + kTile * kLd;     // [16 CT][kLd]: column tile; F_fc[d] in the epilogue
   double* Vs = Cs + 16 * CT * kLd;   // [kChunk]: s_fc on T_d, 0 outside
   double* Aw = As + wid * 16 * kLd;
   const bool active = b0 + 16 * wid < B;  // wave-uniform: this wave has portfolios
 
-  const T* Xd = X + (size_t)d * Q * N;
-  const T* cd = cap + (size_t)d * N;
-  const T* rd = ret + (size_t)d * N;
-  const int16_t* id = ind ? ind + (size_t)d * N : nullptr;
   const double* sd = s_fc + (size_t)d * N;
   const uint8_t* ud = universe ? universe + (size_t)d * N : nullptr;
   const double* Hw = H + (size_t)d * (size_t)h_dstride + (size_t)(b0 + 16 * wid) * N;
@@ -116,13 +110,10 @@ __global__ __launch_bounds__(kThreads) void portfolio_batch_kernel(
     const int n = n0 + lane;
     inr = n < N;
     const int nn = inr ? n : N - 1;
-    cr = cd[nn];
-    rr = rd[nn];
-    jr = id ? (int)id[nn] : 0;
+    day.load_base(nn, cr, rr, jr);
     sr = sd[nn];
     if (ud) ur = ud[nn];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) xr[q] = Xd[(size_t)q * N + nn];
+    day.load_styles(nn, xr);
     if (active) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) hr[r] = Hw[(size_t)min(r, nrow - 1) * N + nn];
@@ -137,8 +128,8 @@ __global__ __launch_bounds__(kThreads) void portfolio_batch_kernel(
   load(0);
   for (int n0 = 0; n0 < N; n0 += kChunk) {
     {  // registers -> LDS: thread (lane, wid) writes the columns c = wid mod 4 of stock n0 + lane
-      bool ok = inr && (ur != 0) && (jr >= 0) && (jr < Pseg) && __builtin_isfinite(cr) &&
-                (cr >= T(0)) && __builtin_isfinite(rr) && __builtin_isfinite(sr) && (sr > 0.0);
+      bool ok = inr && (ur != 0) && MFA_DESIGN_BASE_OK(T, cr, rr, jr, day.Pseg) &&
+                __builtin_isfinite(sr) && (sr > 0.0);
 #pragma unroll
       for (int q = 0; q < Q; ++q) ok = ok && __builtin_isfinite(xr[q]);
       if (wid == 0) {
@@ -181,9 +172,9 @@ __global__ __launch_bounds__(kThreads) void portfolio_batch_kernel(
   // epilogue: F_fc[d] -> Cs (the loop's last barrier has passed), exposures -> this wave's As
   const int kF = K | 1;
   const double* st = stats + (size_t)d * (Q + 2);
-  int bad_stats = 0, bad = 0;
-  for (int q = 0; q <= Q; ++q) bad_stats |= !__builtin_isfinite(st[q]);
-  bad_stats |= !(st[Q] > 0.0);  // a zero pooled sigma has no z-scores either
+  // a zero pooled sigma has no z-scores either
+  const int bad_stats = !stats_finite(st, Q) || !(st[Q] > 0.0);
+  int bad = 0;
   if (F) {
     const double* Fd = F + (size_t)d * K * K;
     for (int e = tid; e < K * K; e += kThreads) {
@@ -209,7 +200,7 @@ __global__ __launch_bounds__(kThreads) void portfolio_batch_kernel(
           if (c == 0) {
             if (b < nrow) realised[row + b] = v;
           } else if (c <= Q) {
-            Aw[b * kF + P + c] = (v - st[c - 1] * hb) * isig;
+            Aw[b * kF + P + c] = unfold_zscore(v, st[c - 1], hb, isig);
           } else if (c < K) {
             Aw[b * kF + c - Q] = v;
           }
@@ -248,13 +239,7 @@ int portfolio_batch_launch(const T* X, const T* cap, const T* ret, const int16_t
                            double* realised, double* held, double* gross, double* exposure,
                            hipStream_t s) {
   const size_t lds = pb_lds_doubles(1 + P + Q) * sizeof(double);
-  static size_t attr = 64 * 1024;  // raise the dynamic-LDS limit once per instantiation and size
-  if (attr < lds) {
-    if (hipError_t err = hipFuncSetAttribute((const void*)portfolio_batch_kernel<Q, T>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-      return (int)err;
-    attr = lds;
-  }
+  if (hipError_t err = raise_dynamic_lds<portfolio_batch_kernel<Q, T>>(lds)) return (int)err;
   hipLaunchKernelGGL((portfolio_batch_kernel<Q, T>), dim3(D, (B + kTile - 1) / kTile),
                      dim3(kThreads), lds, s, X, cap, ret, P > 0 ? ind : nullptr, stats, H,
                      h_dstride, s_fc, F, universe, N, P, B, factor_var, specific_var, realised,
@@ -274,17 +259,13 @@ int portfolio_batch_dispatch(const T* X, const T* cap, const T* ret, const int16
       (B + kTile - 1) / kTile > 65535 || (h_dstride != 0 && h_dstride != (long long)B * N))
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  switch (Q) {
-#define MFA_Q(qq)                                                                              \
-  case qq:                                                                                     \
-    return portfolio_batch_launch<qq, T>(X, cap, ret, ind, stats, H, h_dstride, s_fc, F,       \
-                                         universe, D, N, P, B, factor_var, specific_var,       \
-                                         realised, held, gross, exposure, s);
-    MFA_Q(1) MFA_Q(2) MFA_Q(3) MFA_Q(4) MFA_Q(5) MFA_Q(6) MFA_Q(7) MFA_Q(8)
-    MFA_Q(9) MFA_Q(10) MFA_Q(11) MFA_Q(12) MFA_Q(13) MFA_Q(14) MFA_Q(15) MFA_Q(16)
-#undef MFA_Q
-  }
-  return (int)hipErrorInvalidValue;
+  int err = (int)hipErrorInvalidValue;
+  dispatch_q(Q, [&](auto q) {
+    err = portfolio_batch_launch<decltype(q)::value, T>(
+        X, cap, ret, ind, stats, H, h_dstride, s_fc, F, universe, D, N, P, B, factor_var,
+        specific_var, realised, held, gross, exposure, s);
+  });
+  return err;
 }
 
 }  // namespace

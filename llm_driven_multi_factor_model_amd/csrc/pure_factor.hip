@@ -14,21 +14,21 @@
 //                                rows of C in LDS with (mu, sigma) folded in; non-temporal stores
 //   factor_stats_kernel          residuals, C, f -> se, t      one workgroup per date; order-fixed
 //                                sum (lane -> wave by DPP -> waves)
+// The per-date view of the panel, the regression's validity rule and the fold of (mu, sigma)
+// into a coefficient row are design_row.h's.
 // hipcc --offload-arch=gfx950 -O3, scratch 0 for all of them:
 //   est_cov_kernel                       62 VGPR, dynamic LDS 2 Kr (Kr + 1) + 256 + 3 K doubles
 //                                        (29.9 KB at K = 42, P = 31; 68.5 KB at K = 64, P = 0)
 //   pure_factor_weights_kernel<Q, T>     30 + 6 Q VGPR or fewer (84 at Q = 10, 120 at Q = 16),
 //                                        dynamic LDS nb K doubles (13.8 KB at S = K = 42)
 //   factor_stats_kernel<float / double>  26 VGPR, static LDS 32 B
+#include "design_row.h"
 #include "jacobi.h"
 
 namespace {
 
 using namespace mfa;
 
-constexpr int kThreads = 256;
-constexpr int kMaxK = 64;      // one-wave Jacobi tier (ops.factor_cov.MAX_K)
-constexpr int kMaxQ = 16;
 constexpr int kRowsNB = 64;    // rows of C per pure_factor_weights launch (they live in LDS)
 constexpr int kChunk = 2048;   // stocks per workgroup of pure_factor_weights_kernel
 
@@ -62,8 +62,7 @@ __global__ __launch_bounds__(kThreads) void est_cov_kernel(
   int bad = 0;
   for (int e = tid; e < K * K; e += kThreads) bad |= !__builtin_isfinite(Gd[e]);
   if (tid == 0) {
-    for (int q = 0; q <= Q; ++q) bad |= !__builtin_isfinite(st[q]);
-    bad |= !(st[Q] > 0.0) || !(Gd[0] > 0.0);
+    bad |= !stats_finite(st, Q) || !(st[Q] > 0.0) || !(Gd[0] > 0.0);
     int jp = -1;
     double sp = 1.0;
     if (P > 0) {
@@ -173,33 +172,16 @@ __global__ __launch_bounds__(kThreads) void pure_factor_weights_kernel(
     int nb, double* __restrict__ out) {
   extern __shared__ double pf_lds[];  // [nb][K]
   const int d = blockIdx.x, tid = threadIdx.x;
-  const int Pseg = P > 0 ? P : 1, K = 1 + P + Q;
+  const DesignDate<T> day(X, cap, ret, ind, d, N, P, Q);
+  const int K = 1 + P + Q;
   const double* st = stats + (size_t)d * (Q + 2);
   const double* Cd = C + (size_t)d * K * K;
   int bad = 0;
   for (int e = tid; e < K * K; e += kThreads) bad |= !__builtin_isfinite(Cd[e]);
-  if (tid == 0) {
-    for (int q = 0; q <= Q; ++q) bad |= !__builtin_isfinite(st[q]);
-    bad |= !(st[Q] > 0.0);
-  }
-  if (tid < nb) {  // one thread per row: fold (mu, sigma) into its coefficients
-    const double* cb = Cd + (size_t)sel[b0 + tid] * K;
-    double* cc = pf_lds + tid * K;
-    const double isig = 1.0 / st[Q];
-    double c0 = cb[0];
-    for (int k = 1; k <= P; ++k) cc[k] = cb[k];
-    for (int q = 0; q < Q; ++q) {
-      const double cq = cb[1 + P + q] * isig;
-      cc[1 + P + q] = cq;
-      c0 = fma(-st[q], cq, c0);
-    }
-    cc[0] = c0;
-  }
+  if (tid == 0) bad |= !stats_finite(st, Q) || !(st[Q] > 0.0);
+  // one thread per row: fold (mu, sigma) into its coefficients
+  if (tid < nb) fold_zscore(Cd + (size_t)sel[b0 + tid] * K, st, P, Q, pf_lds + tid * K);
   bad = __syncthreads_or(bad);
-  const T* Xd = X + (size_t)d * Q * N;
-  const T* cd = cap + (size_t)d * N;
-  const T* rd = ret + (size_t)d * N;
-  const int16_t* id = ind ? ind + (size_t)d * N : nullptr;
   double* ob = out + ((size_t)d * NB + b0) * N;
   const int n0 = blockIdx.y * kChunk;
   const int n1 = n0 + kChunk < N ? n0 + kChunk : N;
@@ -207,16 +189,15 @@ __global__ __launch_bounds__(kThreads) void pure_factor_weights_kernel(
     const int m = n + kThreads;
     const bool in2 = m < n1;
     const int m2 = in2 ? m : n;  // the second stock, or the first again (loads stay in bounds)
-    const T ca = cd[n], cb = cd[m2], ra = rd[n], rb = rd[m2];
-    const int ja = id ? (int)id[n] : 0, jb = id ? (int)id[m2] : 0;
-    bool oka = (ja >= 0) && (ja < Pseg) && __builtin_isfinite(ca) && (ca >= T(0)) &&
-               __builtin_isfinite(ra);
-    bool okb = (jb >= 0) && (jb < Pseg) && __builtin_isfinite(cb) && (cb >= T(0)) &&
-               __builtin_isfinite(rb);
+    // the pair's loads are interleaved and the rule is evaluated between them
+    const T ca = day.cap[n], cb = day.cap[m2], ra = day.ret[n], rb = day.ret[m2];
+    const int ja = day.industry(n), jb = day.industry(m2);
+    bool oka = MFA_DESIGN_BASE_OK(T, ca, ra, ja, day.Pseg);
+    bool okb = MFA_DESIGN_BASE_OK(T, cb, rb, jb, day.Pseg);
     double xa[Q], xb[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      const T fa = Xd[(size_t)q * N + n], fb = Xd[(size_t)q * N + m2];
+      const T fa = day.X[(size_t)q * N + n], fb = day.X[(size_t)q * N + m2];
       oka = oka && __builtin_isfinite(fa);
       okb = okb && __builtin_isfinite(fb);
       xa[q] = (double)fa;
@@ -255,18 +236,12 @@ int pure_factor_weights_dispatch(const T* X, const T* cap, const T* ret, const i
   if (chunks > 65535) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)nb * (1 + P + Q) * sizeof(double);
-  switch (Q) {
-#define MFA_Q(qq)                                                                               \
-  case qq:                                                                                      \
-    hipLaunchKernelGGL((pure_factor_weights_kernel<qq, T>), dim3(D, chunks), dim3(kThreads),    \
-                       lds, s, X, cap, ret, P > 0 ? ind : nullptr, stats, C, sel, N, P, NB, b0, \
-                       nb, out);                                                                \
-    break;
-    MFA_Q(1) MFA_Q(2) MFA_Q(3) MFA_Q(4) MFA_Q(5) MFA_Q(6) MFA_Q(7) MFA_Q(8)
-    MFA_Q(9) MFA_Q(10) MFA_Q(11) MFA_Q(12) MFA_Q(13) MFA_Q(14) MFA_Q(15) MFA_Q(16)
-#undef MFA_Q
-  }
-  return (int)hipGetLastError();
+  const bool known = dispatch_q(Q, [&](auto q) {
+    hipLaunchKernelGGL((pure_factor_weights_kernel<decltype(q)::value, T>), dim3(D, chunks),
+                       dim3(kThreads), lds, s, X, cap, ret, P > 0 ? ind : nullptr, stats, C, sel, N,
+                       P, NB, b0, nb, out);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // --------------------------------------------------------------- factor-return standard errors
@@ -283,29 +258,26 @@ __global__ __launch_bounds__(kThreads) void factor_stats_kernel(
     double* __restrict__ sigma2, double* __restrict__ dof) {
   __shared__ double red[4];
   const int d = blockIdx.x, tid = threadIdx.x;
-  const int Pseg = P > 0 ? P : 1, K = 1 + P + Q;
-  const T* Xd = X + (size_t)d * Q * N;
-  const T* cd = cap + (size_t)d * N;
-  const T* rd = ret + (size_t)d * N;
+  const DesignDate<T> day(X, cap, ret, ind, d, N, P, Q);
+  const int K = 1 + P + Q;
   const T* ed = resid + (size_t)d * N;
-  const int16_t* id = ind ? ind + (size_t)d * N : nullptr;
-  double acc = 0.0;
+  double acc[1] = {0.0};
   for (int n = tid; n < N; n += kThreads) {
-    const T c = cd[n], r = rd[n], e = ed[n];
-    const int j = id ? (int)id[n] : 0;
-    bool ok = (j >= 0) && (j < Pseg) && __builtin_isfinite(c) && (c >= T(0)) &&
-              __builtin_isfinite(r) && __builtin_isfinite(e);
-    for (int q = 0; q < Q; ++q) ok = ok && __builtin_isfinite(Xd[(size_t)q * N + n]);
+    T c, r;
+    int j;
+    const T e = ed[n];  // ahead of the industry load and its wait
+    day.load_base(n, c, r, j);
+    bool ok = __builtin_isfinite(e) && day.base_ok(c, r, j);
+    for (int q = 0; q < Q; ++q) ok = ok && __builtin_isfinite(day.X[(size_t)q * N + n]);
     if (!ok) continue;
     const double ev = (double)e;
-    acc = fma(sqrt((double)c), ev * ev, acc);
+    acc[0] = fma(sqrt((double)c), ev * ev, acc[0]);
   }
-  acc = wave_total(acc);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  wave_totals(acc, red);
   __syncthreads();
   const double df = nv[d] - (double)rank[d];
   const bool okd = __builtin_isfinite(df) && df > 0.0;
-  const double s2 = okd ? (((red[0] + red[1]) + red[2]) + red[3]) / df : qnan();
+  const double s2 = okd ? sum4(red, 1, 0) / df : qnan();
   if (tid == 0) {
     sigma2[d] = s2;
     dof[d] = df;
@@ -342,13 +314,7 @@ MFA_API int mfa_est_cov(const double* G, const double* Gs, const double* stats, 
   if (Q < 1 || P < 0 || K > kMaxK || (pivot_mode != 0 && pivot_mode != 1) || (P > 0 && !Gs))
     return (int)hipErrorInvalidValue;
   const size_t lds = est_cov_lds_bytes(K, P);
-  static size_t attr = 64 * 1024;  // raise the dynamic-LDS limit once per size
-  if (attr < lds) {
-    if (hipError_t err = hipFuncSetAttribute((const void*)est_cov_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-      return (int)err;
-    attr = lds;
-  }
+  if (hipError_t err = raise_dynamic_lds<est_cov_kernel>(lds)) return (int)err;
   hipLaunchKernelGGL(est_cov_kernel, dim3(D), dim3(kThreads), lds, (hipStream_t)stream, G,
                      P > 0 ? Gs : G, stats, P, Q, pivot_mode, C, rank);
   return (int)hipGetLastError();

@@ -7,6 +7,8 @@ from llm_driven_multi_factor_model_amd.models.panel import synthetic_panel
 from llm_driven_multi_factor_model_amd.ops import attribution as attr
 from llm_driven_multi_factor_model_amd.ops.cross_section import (pure_factor_portfolio, valid_mask,
                                                                  xs_wls)
+from tests._design_row_cases import (SWEEP_D, SWEEP_N, SWEEP_QS, assert_finite, planted_panel,
+                                     planted_stats, sweep_params)
 
 
 def _panel(D=6, N=120, P=5, Q=4, seed=3):
@@ -62,16 +64,30 @@ def test_risk_model_attribution_cpu():
     assert (r.specific_var[ok] > 0).all() and (r.factor_var[ok] > 0).all()
 
 
+# The 40-date panel with missing cells, then every Q the dispatch knows and the blocked path of
+# wider style sets (17: one style in the second block; 32: two full blocks; 33: a third block) on
+# the planted panel.
+EXPOSURE_CASES = [pytest.param(40, 1000, 31, 10, torch.float32, False, id="k42-missing-cells"),
+                  *(pytest.param(SWEEP_D, SWEEP_N, *s.values, True, id=s.id)
+                    for s in sweep_params(SWEEP_QS + (17, 32, 33)))]
+
+
 @pytest.mark.gpu
-def test_hip_portfolio_exposure_matches_oracle(cuda):
-    p = synthetic_panel(40, 1000, 31, 10, seed=8, missing_frac=0.03)
-    out = xs_wls(p.styles, p.cap, p.ret, p.ind, p.P)
+@pytest.mark.parametrize("D,N,P,Q,dtype,planted", EXPOSURE_CASES)
+def test_hip_portfolio_exposure_matches_oracle(cuda, D, N, P, Q, dtype, planted):
+    if planted:
+        p, _ = planted_panel(D, N, P, Q, dtype)
+        stats = planted_stats(p)
+    else:
+        p = synthetic_panel(D, N, P, Q, seed=8, missing_frac=0.03, dtype=dtype)
+        stats = xs_wls(p.styles, p.cap, p.ret, p.ind, p.P).stats
     g = torch.Generator().manual_seed(2)
     h = torch.rand(p.D, p.N, generator=g, dtype=torch.float64) / p.N
     h[:, ::7] = float("nan")
-    ref = attr.portfolio_exposure(p.styles, p.cap, p.ret, p.ind, h, out.stats, p.P)
+    ref = attr.portfolio_exposure(p.styles, p.cap, p.ret, p.ind, h, stats, p.P)
+    assert_finite(ref)
     gp = p.to(cuda)
-    got = attr.portfolio_exposure(gp.styles, gp.cap, gp.ret, gp.ind, h.to(cuda), out.stats.to(cuda), p.P)
+    got = attr.portfolio_exposure(gp.styles, gp.cap, gp.ret, gp.ind, h.to(cuda), stats.to(cuda), p.P)
     torch.testing.assert_close(got.cpu(), ref, rtol=1e-11, atol=1e-14)
 
 

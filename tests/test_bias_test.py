@@ -26,6 +26,8 @@ from llm_driven_multi_factor_model_amd.models.panel import synthetic_panel
 from llm_driven_multi_factor_model_amd.ops import bias_test as bt
 from llm_driven_multi_factor_model_amd.ops import factor_cov as fc
 from llm_driven_multi_factor_model_amd.ops.cross_section import valid_mask, xs_wls
+from tests._design_row_cases import (SWEEP_D, SWEEP_N, assert_finite, planted_panel,
+                                     planted_stats, sweep_params)
 
 F64 = torch.float64
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,25 +41,31 @@ class Case:
     """Seeded inputs over D = 5 dates: panel (missing_frac = 0.2) + stats, F = A A^T + 0.1 I,
     s with NaN / 0 / negative / inf entries, a universe mask, long-only weights [5, 70, N] with
     NaN entries.  Date 1 has no valid stock (no specific-risk forecast), date 2 a NaN F, date 3
-    a NaN stats row."""
+    a NaN stats row.  ``planted``: D = 2 dates of the Q sweeps' panel
+    (tests/_design_row_cases.py) with none of the three, so that every output is finite."""
 
-    def __init__(self, N, P, Q, dtype, signed=False):
-        D = 5
-        p = synthetic_panel(D, N, P, Q, seed=11 + N, missing_frac=0.2, dtype=dtype)
+    def __init__(self, N, P, Q, dtype, signed=False, planted=False):
+        D = SWEEP_D if planted else 5
+        if planted:
+            p, _ = planted_panel(D, N, P, Q, dtype)
+            self.stats = planted_stats(p)
+        else:
+            p = synthetic_panel(D, N, P, Q, seed=11 + N, missing_frac=0.2, dtype=dtype)
+            self.stats = xs_wls(p.styles, p.cap, p.ret, p.ind, P).stats.to(F64).clone()
+            self.stats[3, 0] = float("nan")
         self.p, self.D, self.N, self.P, self.Q, self.K = p, D, N, P, Q, 1 + P + Q
         K = self.K
-        self.stats = xs_wls(p.styles, p.cap, p.ret, p.ind, P).stats.to(F64).clone()
-        self.stats[3, 0] = float("nan")
         g = torch.Generator().manual_seed(500 + N)
         A = torch.randn(D, K, K, generator=g, dtype=F64) / math.sqrt(K)
         self.F = A @ A.transpose(1, 2) + 0.1 * torch.eye(K, dtype=F64)
-        self.F[2, K // 2, 0] = float("nan")
         s = 0.01 + 0.03 * torch.rand(D, N, generator=g, dtype=F64)
         s[0, 0::11] = float("nan")
         s[0, 1::13] = 0.0
-        s[4, 2::7] = -0.02
-        s[4, 3::17] = float("inf")
-        s[1] = float("nan")
+        if not planted:
+            self.F[2, K // 2, 0] = float("nan")
+            s[4, 2::7] = -0.02
+            s[4, 3::17] = float("inf")
+            s[1] = float("nan")
         self.s = s
         self.universe = torch.rand(D, N, generator=g) < 0.8
         if signed:
@@ -157,6 +165,18 @@ def test_kernel_matches_cpu_path(cuda, P, Q, dtype):
     assert torch.isnan(want.factor_var[3]).all() and torch.isnan(want.exposure[3]).all()
     assert torch.isfinite(want.factor_var[[0, 1, 4]]).all() and (want.factor_var[1] == 0).all()
     assert torch.isfinite(want.realised).all() and torch.isfinite(want.specific_var).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P,Q,dtype", sweep_params())
+def test_kernel_q_sweep(cuda, P, Q, dtype):
+    """Every Q the dispatch knows at N = 300 (five 64-stock chunks, the last one ragged) and
+    B = 17 (a second wave with one portfolio), on the planted panel."""
+    c = _case(SWEEP_N, P, Q, dtype, planted=True)
+    Hd = c.H[:, :17].contiguous()
+    assert_finite(*_forecast(c, "cpu", Hd, True))   # before any GPU run
+    _check(c, cuda, Hd, True)
+    _check(c, cuda, Hd[0], False)
 
 
 @pytest.mark.gpu

@@ -27,6 +27,8 @@ from llm_driven_multi_factor_model_amd.ops import factor_cov as fc
 from llm_driven_multi_factor_model_amd.ops import pure_factor as pf
 from llm_driven_multi_factor_model_amd.ops.cross_section import (pure_factor_portfolio,
                                                                  valid_mask, xs_wls)
+from tests._design_row_cases import (SWEEP_D, SWEEP_N, assert_finite, planted_panel,
+                                     sweep_params)
 
 F64, F32 = torch.float64, torch.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,10 +44,14 @@ def _empty(p, d, j):
 
 
 class Case:
-    """Panel, regression and CPU-path results of one shape."""
+    """Panel, regression and CPU-path results of one shape.  ``planted``: the panel of the Q
+    sweeps (tests/_design_row_cases.py), every date of full rank with finite results."""
 
-    def __init__(self, D, N, P, Q, dtype, nan_stats_date=None):
-        p = synthetic_panel(D, N, P, Q, seed=7, missing_frac=0.05, dtype=dtype)
+    def __init__(self, D, N, P, Q, dtype, nan_stats_date=None, planted=False):
+        if planted:
+            p, _ = planted_panel(D, N, P, Q, dtype)
+        else:
+            p = synthetic_panel(D, N, P, Q, seed=7, missing_frac=0.05, dtype=dtype)
         if P > 1 and D >= 3:
             p = _empty(_empty(p, 1, 0), 2, P - 1)
         self.p, self.D, self.N, self.P, self.Q, self.K = p, D, N, P, Q, 1 + P + Q
@@ -56,6 +62,8 @@ class Case:
         self.est = pf.estimator_cov(*self.args("cpu"))
         self.omega = pf.pure_factor_weights(*self.args("cpu"), self.est.C)
         self.fs = pf.factor_return_stats(*self.args("cpu"), self.xs.f, self.xs.resid, self.est)
+        if planted:
+            assert_finite(self.stats, self.est.C, self.omega, *self.fs)
 
     def args(self, dev, d0=0, d1=None):
         p = self.p.slice_dates(d0, self.D if d1 is None else d1).to(dev)
@@ -385,20 +393,42 @@ def test_estimator_cov_kernel_pivot_modes(cuda, pivot_mode):
     assert bool(torch.isnan(want.C[2]).all()) == (pivot_mode == 1)
 
 
+def _check_weights(c, cuda, d0=0, d1=None):
+    """One row, nine rows and all K rows of Omega against the CPU path (both sides use its C);
+    returns the S = K result."""
+    d1 = c.D if d1 is None else d1
+    K = c.K
+    Cg = c.est.C[d0:d1].to(cuda)
+    for sel in ([K // 2], [int(i) % K for i in range(3, 12)], None):
+        got = pf.pure_factor_weights(*c.args(cuda, d0, d1), Cg, sel)
+        want = c.omega[d0:d1] if sel is None else c.omega[d0:d1][:, sel]
+        _close_per_date(got, want, 1e-11, f"Omega N={c.N} D={d1 - d0} S={want.shape[1]}")
+        assert _same_bits(pf.pure_factor_weights(*c.args(cuda, d0, d1), Cg, sel), got)
+    return got
+
+
+def _check_stats(c, cuda, d0=0, d1=None):
+    d1 = c.D if d1 is None else d1
+    est = pf.EstCov(*(t[d0:d1].to(cuda) for t in c.est))
+    a = (*c.args(cuda, d0, d1), c.xs.f[d0:d1].to(cuda), c.xs.resid[d0:d1].to(cuda), est)
+    got = pf.factor_return_stats(*a)
+    want = pf.FactorStats(*(t[d0:d1] for t in c.fs))
+    for x, y, nm in zip(got, want, got._fields):
+        torch.testing.assert_close(x.cpu(), y, rtol=1e-10, atol=0, equal_nan=True,
+                                   msg=lambda s: f"{nm} N={c.N} D={d1 - d0}: {s}")
+    again = pf.factor_return_stats(*a)
+    assert all(_same_bits(x, y) for x, y in zip(got, again))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
 @pytest.mark.parametrize("P,Q", GPU_PQS)
 def test_weights_kernel_matches_cpu_path(cuda, P, Q, dtype):
     """Bound: 1e-11 of each date's max |Omega| (both sides use the CPU path's C)."""
     K = 1 + P + Q
-    sels = ([K // 2], [int(i) % K for i in range(3, 12)], None)
     for c, d0, d1 in _gpu_cases(P, Q, dtype):
         Cg = c.est.C[d0:d1].to(cuda)
-        for sel in sels:
-            got = pf.pure_factor_weights(*c.args(cuda, d0, d1), Cg, sel)
-            want = c.omega[d0:d1] if sel is None else c.omega[d0:d1][:, sel]
-            _close_per_date(got, want, 1e-11, f"Omega N={c.N} D={d1 - d0} S={want.shape[1]}")
-            assert _same_bits(pf.pure_factor_weights(*c.args(cuda, d0, d1), Cg, sel), got)
+        got = _check_weights(c, cuda, d0, d1)
         if d1 - d0 == 5:   # got is the S = K call: a row alone, and dates [2:5] alone
             for j in (0, K // 2, K - 1):
                 one = pf.pure_factor_weights(*c.args(cuda), Cg, [j])
@@ -413,15 +443,25 @@ def test_weights_kernel_matches_cpu_path(cuda, P, Q, dtype):
 @pytest.mark.parametrize("P,Q", GPU_PQS)
 def test_factor_stats_kernel_matches_cpu_path(cuda, P, Q, dtype):
     for c, d0, d1 in _gpu_cases(P, Q, dtype):
-        est = pf.EstCov(*(t[d0:d1].to(cuda) for t in c.est))
-        a = (*c.args(cuda, d0, d1), c.xs.f[d0:d1].to(cuda), c.xs.resid[d0:d1].to(cuda), est)
-        got = pf.factor_return_stats(*a)
-        want = pf.FactorStats(*(t[d0:d1] for t in c.fs))
-        for x, y, nm in zip(got, want, got._fields):
-            torch.testing.assert_close(x.cpu(), y, rtol=1e-10, atol=0, equal_nan=True,
-                                       msg=lambda s: f"{nm} N={c.N} D={d1 - d0}: {s}")
-        again = pf.factor_return_stats(*a)
-        assert all(_same_bits(x, y) for x, y in zip(got, again))
+        _check_stats(c, cuda, d0, d1)
+
+
+# Every Q the dispatch knows, on the planted panel; and N = 2100, which crosses the weights
+# kernel's 2048-stock chunk and leaves its last 52 stocks without a second stock per thread.
+SWEEP = [*(pytest.param(SWEEP_N, *s.values, id=s.id) for s in sweep_params()),
+         pytest.param(2100, 3, 4, F32, id="p3-q4-f32-n2100")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,P,Q,dtype", SWEEP)
+def test_weights_kernel_q_sweep(cuda, N, P, Q, dtype):
+    _check_weights(_case(SWEEP_D, N, P, Q, dtype, planted=True), cuda)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,P,Q,dtype", SWEEP)
+def test_factor_stats_kernel_q_sweep(cuda, N, P, Q, dtype):
+    _check_stats(_case(SWEEP_D, N, P, Q, dtype, planted=True), cuda)
 
 
 @pytest.mark.gpu

@@ -37,7 +37,14 @@ struct NwDims {
   double lam;
   int org;          // first date of the scanned range: chunk c = [org + c ch, org + (c+1) ch)
   int ch;           // dates per chunk (nw_chunk(K, q): CH unless a chunk's LDS image is too big)
+  double c;         // -ln(lam) of the ROUNDED lam the recurrences use (nw_log_decay)
 };
+
+// 1 - l^n is never formed by subtraction: 1 - pow(l, n) loses tau / (n ln 2) digits (every early
+// date, and every date of a long half-life), so the differences come from expm1(-n c).  c is the
+// log of the rounded l, not ln 2 / tau: Z must weigh the dates exactly as M and S0 do, or the
+// mismatch (n eps) is amplified by mean^2 / var in S0 / Z - mu mu^T.
+double nw_log_decay(double lam) { return -log1p(lam - 1.0); }
 
 // LDS image of a chunk: F rows [t0 - i1 + 1, t1) and M rows [t0 - i1 + 1, t1), then M rows
 // [0, i1 - 1) (the b_i boundary terms, from Mg: the GLOBAL series' first rows).  Rows before
@@ -65,8 +72,9 @@ __device__ void stage_rows(const double* __restrict__ F, const double* __restric
 // Advance the (k,l) state over dates [t0, t1).  s[0] = S0 (group 0 only), s[1 + 2g + {0,1}] =
 // A_{i0+g}[k][l], A_{i0+g}[l][k].  EMIT: write (or add) V for dates in [t_lo, t_hi).
 // tab (EMIT only): per date u of the chunk, tab[(u - t0) * (1 + G)] = 1 / Z(n) and
-// tab[(u - t0) * (1 + G) + 1 + g] = l^(n - i0 - g): one pow per (date, lag) per block instead of
-// per (date, lag, k, l) thread
+// tab[(u - t0) * (1 + G) + 1 + g] = l^(n - i0 - g), stored as l^(n - i0 - g) - 1 where that is
+// negative (nw_emit): one pow / expm1 per (date, lag) per block instead of per (date, lag, k, l)
+// thread
 template <bool EMIT>
 __device__ void nw_run_chunk(const double* Fs, const double* Ms, const double* M0, int t0, int t1,
                              int k, int l, const NwDims& dm, double (&s)[1 + 2 * G],
@@ -101,22 +109,26 @@ __device__ void nw_run_chunk(const double* Fs, const double* Ms, const double* M
       const double* tu = tab + (u - t0) * (1 + G);
       const double iz = tu[0];
       const double mk = Ms[r * K + k] * iz, ml = Ms[r * K + l] * iz;
+      // a non-finite return in column k or l (M stays non-finite from that date on): NaN, where
+      // an inf would leave +-inf whenever the signs of the two inf terms differ
+      const bool dead = !__builtin_isfinite(mk + ml);
       double v = base ? s[0] * iz - mk * ml : 0.0;
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         const int i = dm.i0 + g;
         if (i >= dm.i1) break;
         const double ak = Ms[(r - i) * K + k], al = Ms[(r - i) * K + l];  // a_i = M[u-i]
-        const double dec = tu[1 + g];
+        const double x = tu[1 + g];                   // l^(n-i), or l^(n-i) - 1 where negative
+        const double dec = x < 0.0 ? 1.0 + x : x;
         const double bk = Ms[r * K + k] - dec * M0[(i - 1) * K + k];     // b_i
         const double bl = Ms[r * K + l] - dec * M0[(i - 1) * K + l];
-        const double zi = (1.0 - dec) * il;                               // z_i = Z(n - i)
+        const double zi = (x < 0.0 ? -x : 1.0 - x) * il;                  // z_i = Z(n - i)
         // G_i[k][l] + G_i[l][k]
         const double gkl = s[1 + 2 * g] - ak * ml - mk * bl + zi * mk * ml;
         const double glk = s[2 + 2 * g] - al * mk - ml * bk + zi * ml * mk;
         v = fma(1.0 - (double)i / (q + 1), (gkl + glk) * iz, v);
       }
-      *vo = add ? *vo + v : v;
+      *vo = dead ? qnan() : add ? *vo + v : v;
     }
   }
 }
@@ -193,7 +205,14 @@ __global__ __launch_bounds__(256) void nw_emit(const double* __restrict__ F,
   for (int e = threadIdx.x; e < (t1 - t0) * (1 + G); e += blockDim.x) {
     const int du = e / (1 + G), g = e % (1 + G);
     const double n = (double)(t0 + du + 1);
-    tab[e] = g == 0 ? (1.0 - dm.lam) / (1.0 - pow(dm.lam, n)) : pow(dm.lam, n - (dm.i0 + g - 1));
+    if (g == 0) {
+      tab[e] = (1.0 - dm.lam) / -expm1(-n * dm.c);  // 1 - lam is exact for the rounded lam
+    } else {
+      // l^(n-i) >= 1/2 is stored as l^(n-i) - 1 < 0 (exact to an ulp of the difference), smaller
+      // ones as they are: both l^(n-i) and 1 - l^(n-i) then follow with one rounding
+      const double m = n - (dm.i0 + g - 1);
+      tab[e] = m * dm.c < 0.6931471805599453 ? expm1(-m * dm.c) : pow(dm.lam, m);
+    }
   }
   __syncthreads();
   const int KK = dm.K * dm.K;
@@ -210,6 +229,41 @@ __global__ __launch_bounds__(256) void nw_emit(const double* __restrict__ F,
                      tab);
 }
 
+// Double-double (h + l, |l| <= ulp(h) / 2) helpers of the M scan: error-free sum and product.
+struct dd {
+  double h, l;
+};
+__device__ __forceinline__ dd dd_fast(double s, double e) {  // |s| >= |e|
+  const double h = s + e;
+  return dd{h, e - (h - s)};
+}
+__device__ __forceinline__ dd dd_two_sum(double a, double b) {
+  const double s = a + b, bb = s - a;
+  return dd{s, (a - (s - bb)) + (b - bb)};
+}
+__device__ __forceinline__ dd dd_add(dd a, dd b) {
+  const dd s = dd_two_sum(a.h, b.h);
+  return dd_fast(s.h, s.l + (a.l + b.l));
+}
+__device__ __forceinline__ dd dd_mul(dd a, dd b) {
+  const double p = a.h * b.h;
+  return dd_fast(p, fma(a.h, b.h, -p) + (a.h * b.l + a.l * b.h));
+}
+__device__ __forceinline__ dd dd_axpy(dd a, double lam, double x) {  // a lam + x
+  const double p = a.h * lam;
+  const double e = fma(a.h, lam, -p) + a.l * lam;
+  const dd s = dd_two_sum(p, x);
+  return dd_fast(s.h, s.l + e);
+}
+__device__ __forceinline__ dd dd_powi(double lam, int n) {  // lam^n, n >= 0
+  dd r{1.0, 0.0}, b{lam, 0.0};
+  for (; n > 0; n >>= 1) {
+    if (n & 1) r = dd_mul(r, b);
+    b = dd_mul(b, b);
+  }
+  return r;
+}
+
 // Decayed running sums of K series over rows [t_s, T): M[t][k] = l^(t-t_s+1) init[k] +
 // sum_{t_s<=s<=t} l^(t-s) x[s][k] (no masking; init null = 0; x, M indexed by global row).
 // One wave per column; lane-chunked two-level scan.
@@ -220,22 +274,27 @@ __global__ __launch_bounds__(64) void ew_cumsum_cols(const double* __restrict__ 
   const int k = blockIdx.x, lane = threadIdx.x;
   const int per = (T - t_s + 63) / 64;
   const int a = min(T, t_s + lane * per), b = min(T, a + per);
-  double num = 0.0;
-  for (int t = a; t < b; ++t) num = fma(lam, num, x[(size_t)t * K + k]);
-  double cn = num, dk = pow(lam, (double)(b - a));
+  // The sums and the decay factors are carried as double-doubles and rounded once on store: M
+  // enters V through the lag terms with a weight of up to sum_i (1 - i/(q+1)), so on the first
+  // emitted dates of an autocorrelated series a few ulp of M were the largest error of V.
+  dd num{0.0, 0.0};
+  for (int t = a; t < b; ++t) num = dd_axpy(num, lam, x[(size_t)t * K + k]);
+  dd cn = num, dk = dd_powi(lam, b - a);
   for (int off = 1; off < 64; off <<= 1) {
-    const double pn = __shfl_up(cn, off, 64), pk = __shfl_up(dk, off, 64);
+    const dd pn{__shfl_up(cn.h, off, 64), __shfl_up(cn.l, off, 64)};
+    const dd pk{__shfl_up(dk.h, off, 64), __shfl_up(dk.l, off, 64)};
     if (lane >= off) {
-      cn = fma(pn, dk, cn);
-      dk = dk * pk;
+      cn = dd_add(dd_mul(pn, dk), cn);
+      dk = dd_mul(dk, pk);
     }
   }
-  double en = __shfl_up(cn, 1, 64);
-  if (lane == 0) en = 0.0;
-  if (init) en = fma(pow(lam, (double)(a - t_s)), init[k], en);  // carried-in state, decayed
+  dd en{__shfl_up(cn.h, 1, 64), __shfl_up(cn.l, 1, 64)};
+  if (lane == 0) en = dd{0.0, 0.0};
+  if (init)  // carried-in state, decayed
+    en = dd_add(dd_mul(dd_powi(lam, a - t_s), dd{init[k], 0.0}), en);
   for (int t = a; t < b; ++t) {
-    en = fma(lam, en, x[(size_t)t * K + k]);
-    M[(size_t)t * K + k] = en;
+    en = dd_axpy(en, lam, x[(size_t)t * K + k]);
+    M[(size_t)t * K + k] = en.h + en.l;
   }
 }
 
@@ -301,7 +360,7 @@ size_t nw_lds_doubles(int ch, int K, int q) {
   return (size_t)(2 * (ch + q) + q) * K + (size_t)ch * (1 + G);
 }
 // Dates per chunk: CH, halved (down to 4) while a chunk's LDS image exceeds the CU's 160 KB --
-// a function of (K, q) only, so every shard and rank chunks the same way; K <= ~190 at q = 2
+// a function of (K, q) only, so every shard and rank chunks the same way; K <= 288 at q = 2
 // keeps CH (bitwise the round-5 scan)
 int nw_chunk(int K, int q) {
   int ch = CH;
@@ -355,7 +414,7 @@ MFA_API int mfa_nw_series(const double* F, int T, int K, int q, double tau, int 
   // lag groups [i0, i1): group 0 also carries S0 and writes V; later groups add their lags
   for (int i0 = 1, grp = 0; grp == 0 || i0 <= q; i0 += G, ++grp) {
     const int i1 = std::min(q + 1, i0 + G);
-    NwDims dm{Tn, K, q, i0, i1, lam, 0, ch};
+    NwDims dm{Tn, K, q, i0, i1, lam, 0, ch, nw_log_decay(lam)};
     const int ns = (i0 == 1 ? 1 : 0) + 2 * (i1 - i0);
     const size_t ldsA = (size_t)(ch + i1 - 1) * K * sizeof(double);
     const size_t ldsC = ((size_t)(2 * (ch + i1 - 1) + (i1 - 1)) * K + ch * (1 + G)) * sizeof(double);
@@ -427,7 +486,7 @@ MFA_API int mfa_nw_series_shard(const double* Fsh, const double* Mh, const doubl
   size_t off = 0;
   for (int i0 = 1, grp = 0; grp == 0 || i0 <= q; i0 += G, ++grp) {
     const int i1 = std::min(q + 1, i0 + G);
-    NwDims dm{T1, K, q, i0, i1, lam, T0, ch};
+    NwDims dm{T1, K, q, i0, i1, lam, T0, ch, nw_log_decay(lam)};
     const int ns = (i0 == 1 ? 1 : 0) + 2 * (i1 - i0);
     const size_t ldsA = (size_t)(ch + i1 - 1) * K * sizeof(double);
     const size_t ldsC = ((size_t)(2 * (ch + i1 - 1) + (i1 - 1)) * K + ch * (1 + G)) * sizeof(double);
@@ -455,6 +514,16 @@ MFA_API int mfa_ew_prefix_mean_shard(const double* x, int T, double tau, const d
   if (T <= 0) return 0;
   hipLaunchKernelGGL(ew_prefix_mean, dim3(1), dim3(64), 0, (hipStream_t)stream, x, T,
                      pow(0.5, 1.0 / tau), out, init, tot);
+  return (int)hipGetLastError();
+}
+
+// Mtot[k] = sum_{s<T} l^(T-1-s) x[s][k] of the K columns of x [T][K]: the decayed sum at the last
+// row alone (the sharded scan seeds its halo rows of M from it and runs them forward).
+MFA_API int mfa_ew_cumsum_tail(const double* x, int T, int K, double tau, double* Mtot,
+                               void* stream) {
+  if (T <= 0 || K <= 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(ew_cumsum_tail, dim3(K), dim3(64), 0, (hipStream_t)stream, x, 0, T, K,
+                     pow(0.5, 1.0 / tau), Mtot);
   return (int)hipGetLastError();
 }
 

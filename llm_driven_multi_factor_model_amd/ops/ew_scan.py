@@ -8,9 +8,8 @@ The GPU path (``csrc/ew_scan.hip``) is a blocked decayed-moment scan: O(T K^2 q)
 whole series instead of the reference's O(T^2 K^2 q), one launch per pass and lag group, and an
 output window ``[t_lo, t_hi)`` so a data-parallel rank writes only its own dates.  Any lag
 count is accepted (the reference's ``Newey_West`` takes any ``q < T``; USE4-S uses 5): lags run
-in register groups of 8, so only the chunk's LDS rows bound q (``mfa_nw_max_lags``, ~450 at
-K = 42).  The CPU path is the same
-recurrence in float64 torch.
+in register groups of 8, so only the chunk's LDS rows bound q (``mfa_nw_max_lags``: 159 at
+K = 42, 119 at K = 56).  The CPU path is the same recurrence in float64 torch.
 """
 from __future__ import annotations
 
@@ -63,6 +62,18 @@ def newey_west_series(F: torch.Tensor, q: int = 2, tau: float = 252.0, t_lo: int
     return V
 
 
+def _mask_non_finite(V: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
+    """A non-finite factor return in column k (its decayed sum ``m[k]`` stays non-finite from that
+    date on) makes row and column k of V NaN: an inf would otherwise leave +-inf where the signs
+    of the two inf terms happen to differ."""
+    bad = ~torch.isfinite(m)
+    if bad.any():
+        V = V.clone()
+        V[bad, :] = float("nan")
+        V[:, bad] = float("nan")
+    return V
+
+
 def newey_west_series_reference(F: torch.Tensor, q: int = 2, tau: float = 252.0, t_lo: int = 0,
                                 t_hi: int | None = None) -> torch.Tensor:
     """float64 recurrence (CPU) — identical algebra to the HIP scan, vectorised over K x K."""
@@ -104,7 +115,7 @@ def newey_west_series_reference(F: torch.Tensor, q: int = 2, tau: float = 252.0,
                 i = ii + 1
                 G = (A[ii] - torch.outer(a[ii], mu) - torch.outer(mu, b[ii]) + z[ii] * torch.outer(mu, mu)) / Z
                 V = V + (1.0 - i / (q + 1)) * (G + G.T)
-            out[u - t_lo] = V
+            out[u - t_lo] = _mask_non_finite(V, m)
     return out
 
 
@@ -164,6 +175,8 @@ _native.register("mfa_nw_shard_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c
 _native.register("mfa_nw_series_shard", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_native.register("mfa_ew_cumsum_tail", [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                         C.c_void_p])
 _native.register("mfa_ew_prefix_mean_shard", [C.c_void_p, C.c_int, C.c_double, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p])
 
@@ -226,7 +239,7 @@ def _nw_shard_cpu(Fx: torch.Tensor, h: int, T0: int, q: int, lam: float, st: dic
                 G = (A[ii] - torch.outer(a[ii], mu) - torch.outer(mu, b[ii])
                      + z[ii] * torch.outer(mu, mu)) / Zs
                 Vu = Vu + (1.0 - i / (q + 1)) * (G + G.T)
-            V[du] = Vu
+            V[du] = _mask_non_finite(Vu, m)
     return V if emit else _flat(st)
 
 
@@ -291,15 +304,33 @@ def newey_west_series_sharded(F_own: torch.Tensor, q: int, tau: float, ctx=None,
         if not gpu:
             return _nw_shard_cpu(Fx_, h_, T0_, q, lam, None, emit=False)
         ns = _native.query("mfa_nw_state_doubles", K, q)
-        ctot = torch.empty(ns + K, dtype=torch.float64, device=dev)
+        ctot = torch.empty(ns + K + hq * K, dtype=torch.float64, device=dev)
         ws = torch.empty(max(8, _native.query("mfa_nw_shard_workspace_bytes", T0_, T0_ + n_, K, q)),
                          dtype=torch.uint8, device=dev)
         _native.call("mfa_nw_series_shard", _native.ptr(Fx_), None, None, T0_, T0_ + n_, K, q,
                      float(tau), None, None, _native.ptr(ctot), _native.ptr(ctot[ns:]),
                      _native.ptr(ws), _native.stream(dev))
+        # the own decayed sums at the block's last hq dates (end-aligned), run FORWARD from the
+        # sum at the row before them: later shards build their halo rows of M from these
+        own = Fx_[h_:h_ + n_]
+        base = max(0, n_ - hq)
+        acc = torch.zeros(K, dtype=torch.float64, device=dev)
+        if base:
+            _native.call("mfa_ew_cumsum_tail", _native.ptr(own), base, K, float(tau),
+                         _native.ptr(acc), _native.stream(dev))
+        Mt = ctot[ns + K:].view(hq, K)
+        Mt.zero_()
+        for j in range(base, n_):
+            acc = lam * acc + own[j]
+            Mt[hq - (n_ - j)] = acc
         return ctot
+    if gpu:
+        qmax = _native.query("mfa_nw_max_lags", K)
+        if q > qmax:
+            raise ValueError(f"q={q} exceeds the GPU scan's LDS limit of {qmax} lags at K={K}")
     mine = own_state(Fx, h, T0, D) if D else None
-    nst = (_native.query("mfa_nw_state_doubles", K, q) + K) if gpu else \
+    # GPU state: the kernel's lag moments, the own M total, the own M rows of the last hq dates
+    nst = (_native.query("mfa_nw_state_doubles", K, q) + K + hq * K) if gpu else \
         _flat(_nw_state_cpu(K, q, dev)).numel()
     if mine is None:
         mine = torch.zeros(nst, dtype=torch.float64, device=dev)
@@ -317,13 +348,20 @@ def newey_west_series_sharded(F_own: torch.Tensor, q: int, tau: float, ctx=None,
     # 4. scan of the own dates from the carried state
     if not gpu:
         return _nw_shard_cpu(Fx, h, T0, q, lam, _unflat(cin, K, q), emit=True)
-    ns = nst - K
-    M_in = cin[ns:]
-    Mh = torch.empty(h, K, dtype=torch.float64, device=dev)  # global M rows [lo, T0)
-    if h:
-        Mh[h - 1] = M_in
-        for j in range(h - 1, 0, -1):  # M[t - 1] = (M[t] - f_t) / l
-            Mh[j - 1] = (Mh[j] - Fx[j]) / lam
+    ns = nst - K - hq * K
+    # global M rows [lo, T0): every halo row lies within the last hq dates of its segment, so
+    # M[t] = own M of the segment at t + l^(t + 1 - a) M[a - 1], with M[a - 1] combined forward
+    # over the segments before it.  (Inverting M[t - 1] = (M[t] - f_t) / l from the carried
+    # M[T0 - 1] would grow its rounding by l^-q.)
+    Mh = torch.empty(h, K, dtype=torch.float64, device=dev)
+    Ma = torch.zeros(K, dtype=torch.float64, device=dev)  # M[a - 1] of the current segment
+    for (a, b), o in segs:
+        if b > T0 or a == b:
+            continue
+        Mt = o[ns + K:].view(hq, K)
+        for t in range(max(a, lo), b):
+            Mh[t - lo] = Mt[hq - (b - t)] + (lam ** (t + 1 - a)) * Ma
+        Ma = (lam ** (b - a)) * Ma + o[ns:ns + K]
     first = _rows_from_ends(0, min(q, T1), bounds, heads, tails, hq, K, dev)
     Mg = torch.empty(max(1, first.shape[0]), K, dtype=torch.float64, device=dev)
     acc = torch.zeros(K, dtype=torch.float64, device=dev)

@@ -5,7 +5,7 @@
         --industry data/industry_info.csv --out results/ [--preset reference] [--sims 100] \
         [--checkpoint risk.ckpt] [--resume risk.ckpt] [--attribution equal] [--mongo-uri URI] \
         [--specific-model use4] [--time-scan carry] [--no-deterministic] [--bias-stat 21 --bias-start 1000] \
-        [--bias-test portfolios.csv] [--factor-stats]
+        [--bias-test portfolios.csv] [--factor-stats] [--factor-ic --ic-horizons 1,5,20 --ic-quantiles 5]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m llm_driven_multi_factor_model_amd.cli risk ...
     python -m llm_driven_multi_factor_model_amd.cli factors --prices prices.csv --index index.csv \
         --industry sw_industry.csv --out data/
@@ -123,6 +123,9 @@ def cmd_risk(a):
                                               a.bias_test_window)
     if a.factor_stats:
         paths.update(_write_factor_stats(model, a.out, ctx))
+    if a.factor_ic:
+        hz = [int(h) for h in a.ic_horizons.split(",") if h.strip()]
+        paths.update(_write_factor_ic(model, hz, a.ic_quantiles, a.out, ctx))
     if ctx.rank == 0:
         log.info("stage ms: %s", json.dumps({k: round(v, 3) for k, v in model.times.ms.items()}))
         for k, v in paths.items():
@@ -230,6 +233,49 @@ def _write_factor_stats(model, out_dir: str, ctx):
                             "share_abs_t_gt_2": ((ok & (t > 2)).sum(0) / n).numpy(),
                             "n_obs": n.numpy()}, index=pd.Index(names, name="factor"))
         sig.to_csv(paths["factor_significance"])
+    return paths
+
+
+def _write_factor_ic(model, horizons, quantiles: int, out_dir: str, ctx):
+    """Factor evaluation of the panel's styles (``RiskModel.factor_ic``).  Collective (one gather
+    per column); rank 0 writes ``factor_ic.csv``, one row per (date, factor, horizon): n, ic,
+    rank_ic; and ``factor_ic_summary.csv``, one row per (factor, horizon): the ``ICSummary``
+    fields of ic and rank_ic, the mean return of every quantile bucket over the dates where it is
+    finite (``q1`` lowest) and the mean ``spread`` (top minus bottom bucket)."""
+    from .parallel import dist as pdist
+    ev = model.factor_ic(horizons=horizons, quantiles=quantiles)
+    cols = {"n": ev.n, "ic": ev.ic, "rank_ic": ev.rank_ic, "q_ret": ev.q_ret}
+    if ev.spread is not None:
+        cols["spread"] = ev.spread
+    got = {k: pdist.gather_to_root(v.contiguous(), ctx) for k, v in cols.items()}
+    dates = model._global_dates()
+    paths = {"factor_ic": os.path.join(out_dir, "factor_ic.csv"),
+             "factor_ic_summary": os.path.join(out_dir, "factor_ic_summary.csv")}
+    if ctx.rank == 0:
+        p = model.panel
+        names = list(p.style_names) or [f"style{q}" for q in range(p.Q)]
+        T, S, H = got["ic"].shape
+        idx = pd.DatetimeIndex(dates).strftime("%Y-%m-%d")
+        df = pd.DataFrame({"date": np.repeat(idx.values, S * H),
+                           "factor": np.tile(np.repeat(names, H), T),
+                           "horizon": np.tile(horizons, T * S),
+                           **{k: got[k].cpu().numpy().reshape(-1) for k in ("n", "ic", "rank_ic")}})
+        os.makedirs(out_dir, exist_ok=True)
+        df.to_csv(paths["factor_ic"], index=False)
+
+        def datemean(x):
+            ok = torch.isfinite(x)
+            return (torch.where(ok, x, torch.zeros_like(x)).sum(0) / ok.sum(0)).cpu().numpy()
+        summ = {"factor": np.repeat(names, H), "horizon": np.tile(horizons, S)}
+        for pre, sm in (("ic", ev.summary.ic), ("rank_ic", ev.summary.rank_ic)):
+            for f in sm._fields:
+                summ[f"{pre}_{f}"] = getattr(sm, f).cpu().numpy().reshape(-1)
+        if quantiles > 0:
+            qm = datemean(got["q_ret"])
+            for g in range(quantiles):
+                summ[f"q{g + 1}"] = qm[..., g].reshape(-1)
+            summ["spread"] = datemean(got["spread"]).reshape(-1)
+        pd.DataFrame(summ).to_csv(paths["factor_ic_summary"], index=False)
     return paths
 
 
@@ -388,6 +434,14 @@ def main(argv=None):
                    help="write factor_tstats.csv (date, factor, f, se, t) and "
                         "factor_significance.csv (per factor: mean |t|, share of dates with "
                         "|t| > 2)")
+    r.add_argument("--factor-ic", action="store_true",
+                   help="write factor_ic.csv (date, factor, horizon, n, ic, rank_ic) and "
+                        "factor_ic_summary.csv (per factor and horizon: IC / rank IC mean, std, "
+                        "ICIR, t, hit rate, mean quantile returns, spread) for the styles")
+    r.add_argument("--ic-horizons", default="1,5,20",
+                   help="forward-return horizons of --factor-ic, in dates")
+    r.add_argument("--ic-quantiles", type=int, default=5,
+                   help="quantile buckets of --factor-ic (0: none)")
     r.add_argument("--device", default=None, help="cpu to force the CPU path")
     r.add_argument("--long-specific", action="store_true")
     r.add_argument("--checkpoint", default=None, help="write a resumable checkpoint here")

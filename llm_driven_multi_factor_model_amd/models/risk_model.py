@@ -49,6 +49,25 @@ class Portfolio(NamedTuple):
     expected_return: torch.Tensor | None
 
 
+class EvalSummary(NamedTuple):
+    """:class:`ops.factor_eval.ICSummary` of ``ic`` and of ``rank_ic`` ([S, H] fields)."""
+    ic: ICSummary
+    rank_ic: ICSummary
+
+
+class FactorEval(NamedTuple):
+    """:meth:`RiskModel.factor_ic`: ``n`` int32, ``ic`` / ``rank_ic`` [D_loc, S, H]; ``q_ret`` /
+    ``q_count`` [D_loc, S, H, G]; ``spread`` = ``q_ret[..., -1] - q_ret[..., 0]`` (None when G =
+    0); ``summary`` over the global dates (the same on every rank)."""
+    n: torch.Tensor
+    ic: torch.Tensor
+    rank_ic: torch.Tensor
+    q_ret: torch.Tensor
+    q_count: torch.Tensor
+    spread: torch.Tensor | None
+    summary: EvalSummary
+
+
 class RiskModel:
     """Barra risk model over a (possibly date-sharded) panel.
 
@@ -697,6 +716,64 @@ class RiskModel:
                                  f"{factors!r}")
             factors = named[factors]
         return pf.pure_factor_weights(*args, self.estimator_cov().C, factors)
+
+    # --------------------------------------------------------------- factor evaluation
+    def _eval_inputs(self, signals, universe):
+        p = self.panel
+        x = p.styles if signals is None else signals.to(self.device)
+        if x.dim() != 3 or x.shape[0] != p.D or x.shape[2] != p.N:
+            raise ValueError(f"signals must be [D_loc, S, N] = [{p.D}, S, {p.N}], got "
+                             f"{tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float64)
+        u = p.valid()
+        if universe is not None:
+            u = u & universe.to(device=self.device, dtype=torch.bool)
+        return x, u
+
+    def factor_ic(self, horizons=(1, 5, 20), quantiles: int = 5,
+                  signals: torch.Tensor | None = None, universe: torch.Tensor | None = None,
+                  start: int = 0) -> FactorEval:
+        """Per-date IC, rank IC and quantile-bucket forward returns (:mod:`ops.factor_eval`) of
+        ``signals`` [D_loc, S, N] (default: the panel's raw styles; IC and ranks are invariant to
+        the per-date z-scoring) against the compounded forward returns over ``horizons`` dates,
+        ``panel.ret[d]`` being the first of them.  The universe is ``panel.valid()`` AND the
+        optional ``universe`` [D_loc, N].  Needs no :meth:`regress`.
+
+        Collectives: the ``max(h) - 1`` return rows that follow this rank's block
+        (:func:`parallel.dist.halo_next_rows`), and one gather each of the ``ic`` / ``rank_ic``
+        rows for ``summary``, the :class:`ops.factor_eval.ICSummary` over the global dates >=
+        ``start``, which is the same on every rank and for every world size.  The last ``h - 1``
+        global dates have no ``h``-date forward return: their n is 0."""
+        from ..ops import factor_eval as fe
+        hz = [int(h) for h in horizons]
+        x, u = self._eval_inputs(signals, universe)
+        ret = self.panel.ret.to(torch.float64)
+        tail = pdist.halo_next_rows(ret, max(hz) - 1, self.ctx, self.sizes)
+        y = fe.forward_returns(ret, hz, tail)
+        r = fe.factor_ic(x, y, u, quantiles)
+        s0 = max(0, int(start) - self.T_hist)
+        summ = EvalSummary(*(fe.ic_summary(pdist.all_gather_rows(v.contiguous(), self.ctx,
+                                                                 self.sizes), s0)
+                             for v in (r.ic, r.rank_ic)))
+        spread = r.q_ret[..., -1] - r.q_ret[..., 0] if quantiles > 0 else None
+        return FactorEval(r.n, r.ic, r.rank_ic, r.q_ret, r.q_count, spread, summ)
+
+    def rank_autocorr(self, lag: int = 1, signals: torch.Tensor | None = None,
+                      universe: torch.Tensor | None = None) -> torch.Tensor:
+        """[D_loc, S] Spearman correlation of ``signals[d]`` with ``signals[d - lag]`` (default:
+        the panel's raw styles) over the stocks of date d's universe (``panel.valid()`` AND
+        ``universe``) with both values finite; NaN on the first ``lag`` global dates.  One
+        collective: the ``lag`` signal rows that precede this rank's block."""
+        from ..ops import factor_eval as fe
+        if lag < 1:
+            raise ValueError(f"lag must be >= 1, got {lag}")
+        x, u = self._eval_inputs(signals, universe)
+        D, S, N = x.shape
+        xf = x.reshape(D, S * N)
+        halo = pdist.halo_prev_rows(xf, lag, self.ctx, self.sizes)
+        prev = torch.cat([halo, xf])[:D].reshape(D, S, N).to(torch.float64)
+        return fe.factor_ic(x, prev, u, 0, paired=True).rank_ic
 
     # --------------------------------------------------------------- pandas views
     def factor_returns_frame(self):

@@ -13,6 +13,8 @@ Collective call sites:
                                              barra frame's owned rows as one fp64 block)
   C10 t+1 return across blocks all_gather   ([2, N] first-row value / presence per stock)
   C11 global stock axis        all_reduce   ([N] keep mask, MAX) + [world] kept-date counts
+  C12 forward-return tail      all_gather   (max(h) - 1 first rows of every block's returns,
+                                             halo_next_rows: RiskModel.factor_ic)
   C8 benchmark fences          barrier
   C9 stock-sharded (TP) CS-WLS all_reduce   (D x msize moments, then D x 5 R^2 sums;
                                              ops/xs_sharded.py)
@@ -163,6 +165,32 @@ def halo_prev_rows(x: torch.Tensor, h: int, ctx: DistContext | None = None,
     prev = [out[r * h + h - min(h, sizes[r]):(r + 1) * h] for r in range(ctx.rank)]
     got = torch.cat([nan] + prev)[-h:]
     return got.contiguous()
+
+
+def halo_next_rows(x: torch.Tensor, h: int, ctx: DistContext | None = None,
+                   sizes: list[int] | None = None) -> torch.Tensor:
+    """The ``h`` rows of the GLOBAL series that follow this rank's block, NaN after the last
+    global row: the mirror of :func:`halo_prev_rows` (a forward window's halo).  One collective:
+    every rank contributes its first min(h, D_r) rows, so a block shorter than the halo (or an
+    empty one) is covered by the ranks after it.  Without a process group: all NaN.  Float
+    tensors only."""
+    ctx = ctx or context()
+    shape = (h,) + tuple(x.shape[1:])
+    nan = torch.full(shape, float("nan"), dtype=x.dtype, device=x.device)
+    if h <= 0:
+        return nan[:0]
+    if not ctx.enabled:
+        return nan
+    if sizes is None:
+        sizes = shard_sizes(x.shape[0], ctx)
+    k = min(h, x.shape[0])
+    head = nan.clone()
+    if k:
+        head[:k] = x[:k]
+    out = torch.empty((ctx.world * h,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    dist.all_gather_into_tensor(out, head.contiguous())
+    nxt = [out[r * h:r * h + min(h, sizes[r])] for r in range(ctx.rank + 1, ctx.world)]
+    return torch.cat(nxt + [nan])[:h].contiguous()
 
 
 def broadcast_last_row(x: torch.Tensor, ctx: DistContext | None = None,

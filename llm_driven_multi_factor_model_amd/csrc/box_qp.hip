@@ -18,6 +18,7 @@ using namespace mfa;
 constexpr int kThreads = 256, kWaves = 4;
 constexpr int kMaxK = 64;
 constexpr int kRunning = -1, kOk = 0, kInfeasible = 2, kInvalid = 3;  // ops/box_qp.py
+constexpr int kStalled = 4;  // ops/exposure_qp.py: the trial's projection lost the budget
 constexpr int kRootIters = 100;
 constexpr double kEps = 2.220446049250313e-16;
 constexpr double kInf = __builtin_huge_val();
@@ -417,6 +418,250 @@ __global__ __launch_bounds__(kThreads) void box_step_kernel(
   }
 }
 
+// ------------------------------------------------------- step with exposure equalities
+// The generalised step of ops/exposure_qp.py: the multiplier vector is lambda = (nu_T, mu), the
+// trial's factor coefficients are c = J lambda, and
+//   phi(lambda) = 1/2 sum s^2 h^2 - q'^T h + lambda . J^T x - 1/2 sum d_k lambda_k^2 - tau . lambda
+//   grad = J^T x - d o lambda - tau
+//   H = diag(d) + J^T (G_f - g g^T / sigma) J + rho diag((1 - d) o D_U)
+// (d_k = 1 on the nu slots, 0 on the mu slots; box_step_kernel is the case J = R, d = 1, tau = 0).
+// The multipliers of an unattainable target grow without bound, and with them u = a (q' - X c),
+// until the projection can no longer hold the budget in double precision.  Every trial's budget
+// is therefore tested on x_0 = sum h (the country exposure): a date whose trial misses it is
+// stopped (kStalled) before anything of its state changes; the driver alternates between two
+// projection buffers, `which` names the one that holds the date's last good trial.
+// Dynamic LDS: A, J and Tm = G_f J with the leading dimension K | 1, then ten K-vectors.
+__host__ __device__ constexpr size_t eq_lds_bytes(int K) {
+  return ((size_t)3 * K * (K | 1) + 10 * kMaxK) * sizeof(double);
+}
+
+__global__ __launch_bounds__(kThreads) void eq_step_kernel(
+    const double* __restrict__ G, const double* __restrict__ J, const double* __restrict__ dvec,
+    const double* __restrict__ tau, const double* __restrict__ DU, const double* __restrict__ F,
+    const double* __restrict__ x, const double* __restrict__ pstats,
+    const int* __restrict__ pflag, const double* __restrict__ budget, double tol, int K,
+    int parity, double* __restrict__ nu, double* __restrict__ grad, double* __restrict__ dn,
+    double* __restrict__ c, double* __restrict__ ds, double* __restrict__ rho,
+    double* __restrict__ eta, int* __restrict__ passes, int* __restrict__ status,
+    int* __restrict__ accepted, int* __restrict__ which) {
+  extern __shared__ double eq_lds[];
+  const int kLD = K | 1;
+  double* A = eq_lds;
+  double* Jm = A + K * kLD;
+  double* Tm = Jm + K * kLD;
+  double* nut = Tm + K * kLD;  // trial lambda, then the current lambda
+  double* by = nut + kMaxK;    // J' x
+  double* gt = by + kMaxK;     // gradient at the trial
+  double* gold = gt + kMaxK;   // gradient at the accepted point
+  double* dnv = gold + kMaxK;  // Newton direction
+  double* rn = dnv + kMaxK;    // squared norms of J's rows over the nu slots (diagonal of F_TT)
+  double* dvv = rn + kMaxK;    // d
+  double* tv = dvv + kMaxK;    // tau
+  double* xv = tv + kMaxK;     // x = X' h
+  double* fx = xv + kMaxK;     // F x
+  const int d = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (status[d] != kRunning) return;  // a finished date keeps its state and its c
+  const double* Gd = G + (size_t)d * K * K;
+  const double* Jd = J + (size_t)d * K * K;
+  const double* Fd = F + (size_t)d * K * K;
+  const double* xd = x + (size_t)d * K;
+  const double* td = tau + (size_t)d * K;
+  const double* dud = DU + (size_t)d * K;
+  double* dsd = ds + (size_t)d * 4;  // phi, step, variance and exposure gap of the last trial
+  const int flag = pflag[d];
+  int bad = 0;
+  for (int e = tid; e < K * K; e += kThreads) {
+    const int i = e / K, k = e - i * K;
+    const double gv = Gd[e], jv = Jd[e], fv = Fd[e];
+    bad |= !(__builtin_isfinite(gv) && __builtin_isfinite(jv) && __builtin_isfinite(fv));
+    A[i * kLD + k] = gv;
+    Jm[i * kLD + k] = jv;
+    Tm[i * kLD + k] = fv;  // F, until Tm is formed
+  }
+  for (int e = tid; e < K; e += kThreads) {
+    const double xe = xd[e], te = td[e], de = dud[e], dv = dvec[e];
+    bad |= !(__builtin_isfinite(xe) && __builtin_isfinite(te) && __builtin_isfinite(de) &&
+             __builtin_isfinite(dv));
+    xv[e] = xe;
+    tv[e] = te;
+    dvv[e] = dv;
+  }
+  const double sh2 = pstats[(size_t)d * 3], qh = pstats[(size_t)d * 3 + 1],
+               habs = pstats[(size_t)d * 3 + 2];
+  double rh = rho[d];
+  bad |= !__builtin_isfinite(rh);
+  bad = __syncthreads_or(bad);
+  if (flag == 0) bad |= !(__builtin_isfinite(sh2) && __builtin_isfinite(qh));
+  if (flag != 0 || bad) {
+    if (tid == 0) {
+      status[d] = flag == 1 ? kInfeasible : kInvalid;
+      accepted[d] = 0;
+    }
+    return;
+  }
+  const double phi = dsd[0], step = dsd[1];
+  if (tid < K) {
+    nut[tid] = fma(step, dn[(size_t)d * K + tid], nu[(size_t)d * K + tid]);
+    double s = 0.0, r2 = 0.0, f = 0.0;
+    for (int j = 0; j < K; ++j) {
+      s = fma(Jm[j * kLD + tid], xv[j], s);
+      r2 = fma(Jm[tid * kLD + j] * dvv[j], Jm[tid * kLD + j], r2);
+      f = fma(Tm[tid * kLD + j], xv[j], f);
+    }
+    by[tid] = s;
+    rn[tid] = r2;
+    fx[tid] = f;
+    gold[tid] = grad[(size_t)d * K + tid];
+    dnv[tid] = dn[(size_t)d * K + tid];
+  }
+  __syncthreads();
+  // scalars of the trial, the same serial sums in every thread
+  double nb = 0.0, nn = 0.0, tl = 0.0, xfx = 0.0, gmax = 0.0, gap = 0.0, gd = 0.0, rmax = 0.0;
+  for (int k = 0; k < K; ++k) {
+    const double g = by[k] - dvv[k] * nut[k] - tv[k];
+    nb = fma(nut[k], by[k], nb);
+    nn = fma(dvv[k] * nut[k], nut[k], nn);
+    tl = fma(tv[k], nut[k], tl);
+    xfx = fma(xv[k], fx[k], xfx);
+    if (dvv[k] != 0.0) gmax = fmax(gmax, fabs(g));
+    else gap = fmax(gap, fabs(g));
+    gd = fma(gold[k], dnv[k], gd);
+    rmax = fmax(rmax, rn[k]);
+  }
+  const double phit = 0.5 * sh2 - qh + nb - 0.5 * nn - tl;
+  const int np = passes[d] + 1;
+  if (!(__builtin_isfinite(phit) && __builtin_isfinite(gmax) && __builtin_isfinite(gap))) {
+    if (tid == 0) {
+      status[d] = kInvalid;
+      accepted[d] = 0;
+    }
+    return;
+  }
+  // the trial's budget, half the 1e-12 (sum |h| + |budget|) that a returned row has to meet
+  const double bud = budget[d];
+  if (np > 1 && !(fabs(xv[0] - bud) <= 5e-13 * (habs + fabs(bud)))) {
+    if (tid == 0) {  // uniform; ds, rho, which and the state keep the last good trial
+      status[d] = kStalled;
+      accepted[d] = 0;
+      passes[d] = np;
+    }
+    return;
+  }
+  // converged: the nu block as box_step_kernel, the mu block max |x_S - t| <= tol max(1, sum |h|)
+  const double hs = fmax(1.0, habs);
+  const bool conv = gmax <= tol * hs * sqrt(rmax) && gap <= tol * hs;
+  const bool acc = conv || phit >= phi + 1e-4 * step * gd - 4.0 * kEps * fabs(phit);
+  // rho: a tenth after a step accepted at full length, four times after a cut
+  if (!acc) rh = fmin(4.0 * rh, 1.0);
+  else if (step == 1.0) rh = fmax(rh / 10.0, 1e-14);
+  __syncthreads();  // gold / dnv read by every thread before they change
+  double nstep = 1.0;
+  if (!acc) {  // the maximiser of the parabola through phi(0), phi'(0), phi(step), in [0.1, 0.5] step
+    const double den = 2.0 * (phi + gd * step - phit);
+    double cut = den > 0.0 ? gd * step * step / den : 0.5 * step;
+    if (!(cut == cut)) cut = 0.0;
+    nstep = fmin(fmax(cut, 0.1 * step), 0.5 * step);
+  }
+  if (acc) {
+    if (tid < K) {
+      const double g = by[tid] - dvv[tid] * nut[tid] - tv[tid];
+      gt[tid] = g;
+      nu[(size_t)d * K + tid] = nut[tid];
+      grad[(size_t)d * K + tid] = g;
+    }
+  } else if (tid < K) {
+    nut[tid] = nu[(size_t)d * K + tid];
+  }
+  if (acc && !conv) {
+    // H = diag(d) + J' (G_f - g g' / sigma) J + rho diag((1 - d) D_U); J' g is row 0 of Tm = G_f J
+    for (int e = tid; e < K * K; e += kThreads) {
+      const int i = e / K, k = e - i * K;
+      double s = 0.0;
+      for (int j = 0; j < K; ++j) s = fma(A[i * kLD + j], Jm[j * kLD + k], s);
+      Tm[i * kLD + k] = s;
+    }
+    const double sigma = A[0];
+    const double isg = sigma > 0.0 ? 1.0 / sigma : 0.0;
+    __syncthreads();
+    for (int e = tid; e < K * K; e += kThreads) {
+      const int i = e / K, k = e - i * K;
+      double s = 0.0;
+      if (i == k) s = dvv[i] != 0.0 ? dvv[i] : rh * dud[i];
+      for (int j = 0; j < K; ++j) s = fma(Jm[j * kLD + i], Tm[j * kLD + k], s);
+      A[i * kLD + k] = fma(-Tm[i] * isg, Tm[k], s);
+    }
+    int cbad = 0;
+    for (int k = 0; k < K && !cbad; ++k) {
+      __syncthreads();
+      const double piv = A[k * kLD + k];  // the same value in every thread
+      cbad = !(piv > 0.0) || !__builtin_isfinite(piv);
+      const double inv = 1.0 / sqrt(piv);
+      __syncthreads();
+      if (cbad) break;
+      if (tid >= k && tid < K) A[tid * kLD + k] *= inv;
+      __syncthreads();
+      const int m = K - k - 1;
+      for (int e = tid; e < m * m; e += kThreads) {
+        const int i = k + 1 + e / m, j = k + 1 + e % m;
+        if (j <= i) A[i * kLD + j] = fma(-A[i * kLD + k], A[j * kLD + k], A[i * kLD + j]);
+      }
+    }
+    __syncthreads();
+    if (cbad) {
+      if (tid == 0) {
+        status[d] = kInvalid;
+        accepted[d] = 0;
+      }
+      return;
+    }
+    if (wid == 0) {  // H dn = grad, lane i holds row i
+      const bool in = lane < K;
+      const int li = in ? lane : 0;
+      double p = in ? gt[li] : 0.0;
+      for (int j = 0; j < K; ++j) {
+        const double yj = __shfl(p, j, kWave) / A[j * kLD + j];
+        if (lane == j) p = yj;
+        else if (lane > j && in) p = fma(-A[li * kLD + j], yj, p);
+      }
+      for (int j = K - 1; j >= 0; --j) {
+        const double xj = __shfl(p, j, kWave) / A[j * kLD + j];
+        if (lane == j) p = xj;
+        else if (lane < j) p = fma(-A[j * kLD + li], xj, p);
+      }
+      if (in) {
+        dnv[lane] = p;
+        dn[(size_t)d * K + lane] = p;
+      }
+    }
+  }
+  __syncthreads();
+  if (conv) nstep = 0.0;  // c = J lambda
+  if (tid < K) {
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s = fma(Jm[tid * kLD + k], fma(nstep, dnv[k], nut[k]), s);
+    c[(size_t)d * K + tid] = s;
+    if (conv) {  // eta = -mu + (F x)_S on the mu slots: (Sigma h - q)_n = gamma + (X_S eta)_n
+      double e = 0.0;
+      if (dvv[tid] == 0.0) {
+        for (int j = 0; j < K; ++j) e = fma(Jm[j * kLD + tid], fx[j], e);
+        e -= nut[tid];
+      }
+      eta[(size_t)d * K + tid] = e;
+    }
+  }
+  if (tid == 0) {
+    if (acc) dsd[0] = phit;
+    dsd[1] = nstep;
+    dsd[2] = sh2 + xfx;
+    dsd[3] = gap;
+    rho[d] = rh;
+    passes[d] = np;
+    accepted[d] = acc;
+    which[d] = parity;
+    if (conv) status[d] = kOk;
+  }
+}
+
 }  // namespace
 
 // u, a, lo, hi, q, h, w [D][N] f64; budget, gamma [D] (gamma: warm start in, root out);
@@ -460,5 +705,33 @@ MFA_API int mfa_box_step(const double* G, const double* lam, const double* U, co
   }
   hipLaunchKernelGGL(box_step_kernel, dim3(D), dim3(kThreads), lds, (hipStream_t)stream, G, lam,
                      U, x, pstats, pflag, tol, K, nu, grad, dn, c, ds, passes, status, accepted);
+  return (int)hipGetLastError();
+}
+
+// The step with exposure equalities.  G, x, pstats, pflag as mfa_box_step; J, F [D][K][K]; dvec
+// [K] (1 on the nu slots, 0 on the mu slots); tau, DU [D][K]; state as mfa_box_step with nu
+// holding lambda and ds [D][4] = (phi, step, variance, exposure gap of the last trial), plus rho
+// [D] and eta [D][K] (written when a date converges: the multipliers on the mu slots, 0 on the
+// others); budget [D]; which [D] is set to `parity` for every date whose trial holds the budget,
+// a date whose trial misses it gets status 4 and keeps everything else.  K <= 64.
+MFA_API int mfa_eq_step(const double* G, const double* J, const double* dvec, const double* tau,
+                        const double* DU, const double* F, const double* x, const double* pstats,
+                        const int* pflag, const double* budget, double tol, int D, int K,
+                        int parity, double* nu, double* grad, double* dn, double* c, double* ds,
+                        double* rho, double* eta, int* passes, int* status, int* accepted,
+                        int* which, void* stream) {
+  if (D <= 0) return 0;
+  if (K < 1 || K > kMaxK) return (int)hipErrorInvalidValue;
+  const size_t lds = eq_lds_bytes(K);
+  static size_t attr = 64 * 1024;  // raise the dynamic-LDS limit once per size
+  if (attr < lds) {
+    if (hipError_t err = hipFuncSetAttribute((const void*)eq_step_kernel,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+      return (int)err;
+    attr = lds;
+  }
+  hipLaunchKernelGGL(eq_step_kernel, dim3(D), dim3(kThreads), lds, (hipStream_t)stream, G, J, dvec,
+                     tau, DU, F, x, pstats, pflag, budget, tol, K, parity, nu, grad, dn, c, ds, rho,
+                     eta, passes, status, accepted, which);
   return (int)hipGetLastError();
 }

@@ -40,13 +40,17 @@ class MinVariance(NamedTuple):
 class Portfolio(NamedTuple):
     """:meth:`RiskModel.optimize`: ``weights`` [D_loc, N], ``variance`` [D_loc] (float64),
     ``passes`` / ``status`` [D_loc] (int32, the codes of :mod:`ops.box_qp`), ``active_variance``
-    [D_loc] (None without a benchmark), ``expected_return`` [D_loc] (None without alpha)."""
+    [D_loc] (None without a benchmark), ``expected_return`` [D_loc] (None without alpha);
+    with ``neutral``: ``exposure_gap`` [D_loc] = max |x_S - t| and ``eta`` [D_loc, m], the
+    multipliers of the exposure constraints (:mod:`ops.exposure_qp`), None otherwise."""
     weights: torch.Tensor
     variance: torch.Tensor
     passes: torch.Tensor
     status: torch.Tensor
     active_variance: torch.Tensor | None
     expected_return: torch.Tensor | None
+    exposure_gap: torch.Tensor | None = None
+    eta: torch.Tensor | None = None
 
 
 class EvalSummary(NamedTuple):
@@ -561,7 +565,8 @@ class RiskModel:
     def optimize(self, alpha: torch.Tensor | None = None, risk_aversion: float = 1.0,
                  lower=0.0, upper=1.0, benchmark: torch.Tensor | None = None, budget=1.0,
                  which: str = "vra", specific_vol: torch.Tensor | str = "shrunk",
-                 universe: torch.Tensor | None = None, **solver) -> Portfolio:
+                 universe: torch.Tensor | None = None, neutral=None, exposure=None,
+                 **solver) -> Portfolio:
         """Box-constrained portfolio of every date (:func:`ops.box_qp.box_qp`): minimise
         ``1/2 h^T Sigma h - q^T h`` subject to ``sum h = budget`` and ``lower <= h <= upper`` on
         the universe, with ``q = alpha / risk_aversion`` (+ ``Sigma h_b`` when a ``benchmark`` is
@@ -570,7 +575,14 @@ class RiskModel:
         ``which`` / ``specific_vol`` / ``universe`` as in :meth:`min_variance`; ``solver``
         passes ``tol``, ``max_passes`` and ``check_every`` on.  Infeasible dates and dates with
         an invalid covariance give NaN rows (see ``status``).  Per date: the only collective is
-        the one ``"shrunk"`` makes."""
+        the one ``"shrunk"`` makes.
+
+        ``neutral`` adds the equality constraints ``(X^T h)_k = t_k`` on a set of factors
+        (:func:`ops.exposure_qp.exposure_qp`): an index list into the K factors without the
+        country, or ``"industries"``, ``"styles"``, ``"all"`` (every factor but the country).
+        ``exposure`` [m] or [D_loc, m] are the targets; None means the exposures of
+        ``benchmark`` restricted to the universe (active-neutral; ``ValueError`` without a
+        benchmark).  ``neutral=None`` is the box-constrained problem alone."""
         from ..ops import box_qp as bq
         from ..ops import factor_cov as fc
         cov, sv = self._cov_inputs(which, specific_vol)
@@ -585,7 +597,26 @@ class RiskModel:
             hb = self._rows(benchmark)
             Shb = fc.apply_cov(*args, cov, sv, hb, universe)
             q = q + Shb
-        r = bq.box_qp(*args, cov, sv, q, lower, upper, budget, universe, **solver)
+        gap = eta = None
+        if neutral is None:
+            if exposure is not None:
+                raise ValueError("exposure needs neutral, the factors it constrains")
+            r = bq.box_qp(*args, cov, sv, q, lower, upper, budget, universe, **solver)
+        else:
+            from ..ops import exposure_qp as eq
+            sel = self._neutral_factors(neutral)
+            if exposure is None:
+                if hb is None:
+                    raise ValueError("neutral without exposure targets needs a benchmark")
+                m = fc.universe_mask(p.styles, p.cap, p.ret, p.ind, p.P, sv, universe)
+                hz = torch.where(m, torch.nan_to_num(hb, nan=0.0, posinf=0.0, neginf=0.0),
+                                 torch.zeros_like(q))
+                exposure = fc.factor_xty(*args, hz[:, None])[:, 0][:, sel]
+            else:
+                exposure = torch.as_tensor(exposure, dtype=torch.float64, device=self.device)
+            r = eq.exposure_qp(*args, cov, sv, sel, exposure, q, lower, upper, budget, universe,
+                               **solver)
+            gap, eta = r.exposure_gap, r.eta
         active = ret = None
         if hb is not None:   # (h - h_b)^T Sigma (h - h_b), h_b restricted to the universe
             m = fc.universe_mask(p.styles, p.cap, p.ret, p.ind, p.P, sv, universe)
@@ -595,7 +626,18 @@ class RiskModel:
             active = (e * fc.apply_cov(*args, cov, sv, e, universe)).sum(-1)
         if al is not None:
             ret = (al * r.weights).sum(-1)
-        return Portfolio(r.weights, r.variance, r.passes, r.status, active, ret)
+        return Portfolio(r.weights, r.variance, r.passes, r.status, active, ret, gap, eta)
+
+    def _neutral_factors(self, neutral) -> list[int]:
+        P, K = self.panel.P, self.K
+        if isinstance(neutral, str):
+            named = {"industries": list(range(1, 1 + P)), "styles": list(range(1 + P, K)),
+                     "all": list(range(1, K))}
+            if neutral not in named:
+                raise ValueError(f"neutral must be an index list or one of {sorted(named)}, got "
+                                 f"{neutral!r}")
+            return named[neutral]
+        return [int(k) for k in neutral]
 
     def predicted_beta(self, h_bench: torch.Tensor, which: str = "vra",
                        specific_vol: torch.Tensor | str = "shrunk",

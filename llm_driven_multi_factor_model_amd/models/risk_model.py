@@ -42,7 +42,9 @@ class Portfolio(NamedTuple):
     ``passes`` / ``status`` [D_loc] (int32, the codes of :mod:`ops.box_qp`), ``active_variance``
     [D_loc] (None without a benchmark), ``expected_return`` [D_loc] (None without alpha);
     with ``neutral``: ``exposure_gap`` [D_loc] = max |x_S - t| and ``eta`` [D_loc, m], the
-    multipliers of the exposure constraints (:mod:`ops.exposure_qp`), None otherwise."""
+    multipliers of the exposure constraints (:mod:`ops.exposure_qp`), None otherwise; with
+    ``tcost``: ``turnover`` [D_loc] = sum |h - prev| and ``cost`` [D_loc] = sum tcost |h - prev|
+    (:class:`ops.box_qp.BoxQPCost`), None otherwise."""
     weights: torch.Tensor
     variance: torch.Tensor
     passes: torch.Tensor
@@ -51,6 +53,8 @@ class Portfolio(NamedTuple):
     expected_return: torch.Tensor | None
     exposure_gap: torch.Tensor | None = None
     eta: torch.Tensor | None = None
+    turnover: torch.Tensor | None = None
+    cost: torch.Tensor | None = None
 
 
 class EvalSummary(NamedTuple):
@@ -566,6 +570,7 @@ class RiskModel:
                  lower=0.0, upper=1.0, benchmark: torch.Tensor | None = None, budget=1.0,
                  which: str = "vra", specific_vol: torch.Tensor | str = "shrunk",
                  universe: torch.Tensor | None = None, neutral=None, exposure=None,
+                 prev=None, tcost=None, dates: tuple[int, int] | None = None,
                  **solver) -> Portfolio:
         """Box-constrained portfolio of every date (:func:`ops.box_qp.box_qp`): minimise
         ``1/2 h^T Sigma h - q^T h`` subject to ``sum h = budget`` and ``lower <= h <= upper`` on
@@ -582,26 +587,48 @@ class RiskModel:
         country, or ``"industries"``, ``"styles"``, ``"all"`` (every factor but the country).
         ``exposure`` [m] or [D_loc, m] are the targets; None means the exposures of
         ``benchmark`` restricted to the universe (active-neutral; ``ValueError`` without a
-        benchmark).  ``neutral=None`` is the box-constrained problem alone."""
+        benchmark).  ``neutral=None`` is the box-constrained problem alone.
+
+        ``prev`` / ``tcost`` (a scalar, [N] or [D_loc, N] each; both or neither) add the linear
+        trading cost ``sum_n tcost_n |h_n - prev_n|`` to the objective (:mod:`ops.tcost_qp`):
+        ``prev`` are the holdings before the trade, ``tcost`` = +inf freezes a name; the result
+        carries ``turnover`` and ``cost``.  ``dates`` = (a, b) solves the local dates a..b-1
+        only: every per-date argument is still given for the whole block and is cut to those
+        rows, and the result has b - a rows (:meth:`rebalance` solves one date at a time)."""
         from ..ops import box_qp as bq
         from ..ops import factor_cov as fc
         cov, sv = self._cov_inputs(which, specific_vol)
-        p = self.panel
-        args = (p.styles, p.cap, p.ret, p.ind, self.stats, p.P)
+        p, stats = self.panel, self.stats
+        if dates is not None:
+            a0, b0 = dates
+            D_all = p.D
+            p, stats, cov = p.slice_dates(a0, b0), stats[a0:b0], cov[a0:b0]
+
+            def cut(t, per_date_dim=2):
+                if isinstance(t, torch.Tensor) and t.dim() >= per_date_dim \
+                        and t.shape[0] == D_all:
+                    return t[a0:b0]
+                return t
+            sv, alpha, benchmark, lower, upper, universe, exposure, prev, tcost = map(
+                cut, (sv, alpha, benchmark, lower, upper, universe, exposure, prev, tcost))
+            budget = cut(budget, 1)
+        rows = lambda t: t.to(device=self.device, dtype=torch.float64).expand(p.D, -1)  # noqa: E731
+        args = (p.styles, p.cap, p.ret, p.ind, stats, p.P)
         q = torch.zeros(p.D, p.N, dtype=torch.float64, device=self.device)
         al = hb = Shb = None
+        tc = {} if tcost is None and prev is None else dict(prev=prev, tcost=tcost)
         if alpha is not None:
-            al = torch.nan_to_num(self._rows(alpha), nan=0.0, posinf=0.0, neginf=0.0)
+            al = torch.nan_to_num(rows(alpha), nan=0.0, posinf=0.0, neginf=0.0)
             q = q + al / risk_aversion
         if benchmark is not None:
-            hb = self._rows(benchmark)
+            hb = rows(benchmark)
             Shb = fc.apply_cov(*args, cov, sv, hb, universe)
             q = q + Shb
         gap = eta = None
         if neutral is None:
             if exposure is not None:
                 raise ValueError("exposure needs neutral, the factors it constrains")
-            r = bq.box_qp(*args, cov, sv, q, lower, upper, budget, universe, **solver)
+            r = bq.box_qp(*args, cov, sv, q, lower, upper, budget, universe, **solver, **tc)
         else:
             from ..ops import exposure_qp as eq
             sel = self._neutral_factors(neutral)
@@ -615,7 +642,7 @@ class RiskModel:
             else:
                 exposure = torch.as_tensor(exposure, dtype=torch.float64, device=self.device)
             r = eq.exposure_qp(*args, cov, sv, sel, exposure, q, lower, upper, budget, universe,
-                               **solver)
+                               **solver, **tc)
             gap, eta = r.exposure_gap, r.eta
         active = ret = None
         if hb is not None:   # (h - h_b)^T Sigma (h - h_b), h_b restricted to the universe
@@ -626,7 +653,54 @@ class RiskModel:
             active = (e * fc.apply_cov(*args, cov, sv, e, universe)).sum(-1)
         if al is not None:
             ret = (al * r.weights).sum(-1)
-        return Portfolio(r.weights, r.variance, r.passes, r.status, active, ret, gap, eta)
+        return Portfolio(r.weights, r.variance, r.passes, r.status, active, ret, gap, eta,
+                         *((r.turnover, r.cost) if tc else ()))
+
+    def rebalance(self, start: torch.Tensor | None = None, drift: bool = True,
+                  **optimize_kwargs) -> Portfolio:
+        """A path of holdings over the local dates: date t is solved by :meth:`optimize`
+        (``optimize_kwargs``, which must hold ``tcost``) with ``prev`` = the holdings that date
+        t - 1 ended with; the first date starts from ``start`` [N] (zeros: from cash).
+
+        With ``drift`` the carried weights first move with the market: p = h o (1 + r) / (1 +
+        sum h r) with r = ``nan_to_num(ret[t - 1])``, the panel's return row of the date the
+        holdings come from.  These are fractions of the net asset value, valid for any budget,
+        0 included.  A date that ends ``INFEASIBLE`` or ``INVALID`` (a NaN row) does not trade:
+        the holdings are carried through it.  Returns the stacked :class:`Portfolio`; its
+        ``turnover`` / ``cost`` are those of every date's trade.
+
+        This is a sequential loop, one date after the other: D_loc times the launches-per-pass
+        sequence of a one-date :meth:`optimize`, not a batched path, so a workgroup-per-date
+        kernel runs on one CU.  Each date depends on the one before, so the method is
+        single-process only (``RuntimeError`` with more than one rank).  ``specific_vol`` is
+        resolved once, before the loop."""
+        from ..ops import box_qp as bq
+        if self.ctx.world > 1:
+            raise RuntimeError("rebalance walks the dates in order and is single-process only; "
+                               f"this run has {self.ctx.world} ranks")
+        if optimize_kwargs.get("tcost") is None:
+            raise ValueError("rebalance needs tcost (0.0 for none)")
+        if "prev" in optimize_kwargs or "dates" in optimize_kwargs:
+            raise ValueError("rebalance sets prev and dates itself")
+        p = self.panel
+        kw = dict(optimize_kwargs)
+        sv = kw.get("specific_vol", "shrunk")
+        if isinstance(sv, str):
+            kw["specific_vol"] = self._specific_vol_named(sv).to(self.device)
+        hold = torch.zeros(p.N, dtype=torch.float64, device=self.device) if start is None \
+            else start.to(device=self.device, dtype=torch.float64).clone()
+        out = []
+        for t in range(p.D):
+            if drift and t > 0:
+                r = torch.nan_to_num(p.ret[t - 1].double(), nan=0.0, posinf=0.0, neginf=0.0)
+                hold = hold * (1.0 + r) / (1.0 + (hold * r).sum())
+            res = self.optimize(prev=hold, dates=(t, t + 1), **kw)
+            out.append(res)
+            if int(res.status[0]) < bq.INFEASIBLE:
+                hold = res.weights[0]
+        if not out:
+            return self.optimize(prev=hold, dates=(0, 0), **kw)
+        return Portfolio(*(None if f[0] is None else torch.cat(f) for f in zip(*out)))
 
     def _neutral_factors(self, neutral) -> list[int]:
         P, K = self.panel.P, self.K

@@ -33,6 +33,9 @@ One pass on the GPU is five launches with no host synchronisation: ``factor_appl
 ``box_project`` (gamma, h, w), ``factor_gram`` (G_f), ``factor_xty`` (X^T h) and ``box_step``
 (``csrc/box_qp.hip``); K = 1 + P + Q <= 64 and Q <= 16 as in :mod:`.factor_cov`.  CPU tensors take
 the float64 torch transcription below (dense ``X_d``; any K), which is also the tests' oracle.
+
+With ``prev`` / ``tcost`` the objective gains the linear trading cost ``sum_n kappa_n |h_n -
+p_n|``; only the projection changes (:mod:`.tcost_qp`), the step is the one below.
 """
 from __future__ import annotations
 
@@ -65,6 +68,20 @@ class BoxQP(NamedTuple):
     variance: torch.Tensor
     passes: torch.Tensor
     status: torch.Tensor
+
+
+class BoxQPCost(NamedTuple):
+    """:func:`box_qp` with ``prev`` / ``tcost``: the fields of :class:`BoxQP`, then ``turnover``
+    [D] = sum_n |h_n - p_n| over all N stocks (a non-finite p counts as 0, so the forced sale of
+    a name that left the universe is counted) and ``cost`` [D], the same sum weighted by kappa
+    (a stock with a non-finite kappa counts 0); NaN where the weights are."""
+    weights: torch.Tensor
+    gamma: torch.Tensor
+    variance: torch.Tensor
+    passes: torch.Tensor
+    status: torch.Tensor
+    turnover: torch.Tensor
+    cost: torch.Tensor
 
 
 class Projection(NamedTuple):
@@ -315,7 +332,8 @@ def box_step(G, lam, U, x, pstats, pflag, state: StepState, tol: float) -> StepS
 # ------------------------------------------------------------------------------------- driver
 class Problem(NamedTuple):
     """What every pass of :func:`box_qp` reads: the panel, ``a`` (0 outside the universe), the
-    bounds, ``q``, ``budget`` [D] and the eigenpairs of F."""
+    bounds, ``q``, ``budget`` [D] and the eigenpairs of F; with trading costs also ``prev`` and
+    ``kappa`` [D, N] (:mod:`.tcost_qp`), None without."""
     panel: tuple
     a: torch.Tensor
     lo: torch.Tensor
@@ -325,18 +343,32 @@ class Problem(NamedTuple):
     lam: torch.Tensor
     U: torch.Tensor
     Xd: torch.Tensor | None    # dense design matrix (torch path only)
+    prev: torch.Tensor | None = None
+    kappa: torch.Tensor | None = None
 
 
 def make_problem(X, cap, ret, ind, stats, P, F, spec_vol, q=None, lower=0.0, upper=1.0,
-                 budget=1.0, universe=None, dense: bool | None = None) -> Problem:
+                 budget=1.0, universe=None, dense: bool | None = None, prev=None,
+                 tcost=None) -> Problem:
     """The per-call set-up of :func:`box_qp` (same arguments): broadcast bounds and ``q``, ``a``
     masked to the universe, ``eigh(F)``; ``dense`` also builds the design matrix (default: on
-    the CPU)."""
+    the CPU).  With ``prev`` / ``tcost``: a non-finite prev becomes 0, and a stock with kappa =
+    +inf ("do not trade") gets lo = hi = clip(prev, lo, hi) and kappa = 0, so that no infinity
+    reaches the projection."""
     D, Q, N = X.shape
     K = 1 + P + Q
     dev = X.device
     dense = (not X.is_cuda) if dense is None else dense
     lo, hi = _rows(lower, D, N, dev, "lower"), _rows(upper, D, N, dev, "upper")
+    pv = kap = None
+    if tcost is not None:
+        pv = torch.nan_to_num(_rows(prev, D, N, dev, "prev"), nan=0.0, posinf=0.0, neginf=0.0)
+        kap = _rows(tcost, D, N, dev, "tcost")
+        frozen = kap == _INF
+        pin = torch.minimum(torch.maximum(pv, lo), hi)
+        fix = frozen & (lo <= hi)          # lo > hi stays what it is: infeasible
+        lo, hi = torch.where(fix, pin, lo), torch.where(fix, pin, hi)
+        kap = torch.where(frozen, torch.zeros_like(kap), kap).contiguous()
     q = _rows(0.0 if q is None else q, D, N, dev, "q")
     bud = torch.as_tensor(budget, dtype=torch.float64, device=dev).expand(D).contiguous()
     a, _ = fc._weights(X, cap, ret, ind, P, spec_vol, universe)
@@ -351,17 +383,25 @@ def make_problem(X, cap, ret, ind, stats, P, F, spec_vol, q=None, lower=0.0, upp
         lam, U = F.new_empty(0, K), F.new_empty(0, K, K)
     Xd = fc.design_matrix(X, cap, ret, ind, torch.nan_to_num(stats), P, m) if dense else None
     return Problem((X, cap, ret, ind, stats, P), a, lo, hi, q, bud, lam.contiguous(),
-                   U.contiguous(), Xd)
+                   U.contiguous(), Xd, pv, kap)
 
 
 def run_trial(pb: Problem, st: StepState, pj: Projection, *, stream_rows: bool = False):
     """The trial ``c`` of ``st`` for every running date: u, the projection (into ``pj``), and
-    ``(G_f, X^T h)``.  On the GPU: four launches (apply, project, Gram, X^T h)."""
+    ``(G_f, X^T h)``.  On the GPU: four launches (apply, project, Gram, X^T h).  A problem
+    with ``prev`` / ``kappa`` takes the projection of :mod:`.tcost_qp`."""
     X, cap, ret, ind, stats, P = pb.panel
+    if pb.kappa is not None:
+        from . import tcost_qp as tc
+        tcp = tc.TcProjection(pj, pj.gamma.new_zeros(pj.gamma.shape))
     if pb.Xd is None:
         u = fc.factor_apply(*pb.panel, pb.a, -pb.a, pb.q[:, None], st.c[:, None, :])[:, 0]
-        box_project(u, pb.a, pb.lo, pb.hi, pb.budget, pb.q, None, st.status, out=pj,
-                    stream_rows=stream_rows)
+        if pb.kappa is not None:
+            tc.tc_project(u, pb.a, pb.lo, pb.hi, pb.budget, pb.prev, pb.kappa, pb.q, None,
+                          st.status, out=tcp, stream_rows=stream_rows)
+        else:
+            box_project(u, pb.a, pb.lo, pb.hi, pb.budget, pb.q, None, st.status, out=pj,
+                        stream_rows=stream_rows)
         G = fc.factor_gram(*pb.panel, pj.w)
         x = fc.factor_xty(*pb.panel, pj.h[:, None])[:, 0]
         return G, x
@@ -369,7 +409,11 @@ def run_trial(pb: Problem, st: StepState, pj: Projection, *, stream_rows: bool =
     u = pb.a * (torch.nan_to_num(pb.q, nan=0.0, posinf=0.0, neginf=0.0)
                 - torch.einsum("dnk,dk->dn", pb.Xd, st.c))
     u[~ok] = float("nan")
-    _project_into(pj, u, pb.a, pb.lo, pb.hi, pb.q, pb.budget, st.status)
+    if pb.kappa is not None:
+        tc._tc_project_into(tcp, u, pb.a, pb.lo, pb.hi, pb.q, pb.budget, pb.prev, pb.kappa,
+                            st.status)
+    else:
+        _project_into(pj, u, pb.a, pb.lo, pb.hi, pb.q, pb.budget, st.status)
     G = torch.einsum("dnk,dn,dnl->dkl", pb.Xd, pj.w, pb.Xd)
     G[~ok] = float("nan")
     return G, torch.einsum("dnk,dn->dk", pb.Xd, pj.h)
@@ -399,6 +443,23 @@ def _project_into(pj, u, a, lo, hi, q, bud, status):
     pj.flag.copy_(torch.where(run, flag, pj.flag))
 
 
+def check_tcost(prev, tcost) -> None:
+    if (prev is None) != (tcost is None):
+        raise ValueError("prev and tcost go together: the trading cost is sum tcost |h - prev|, "
+                         f"got only {'prev' if tcost is None else 'tcost'}")
+
+
+def trade_stats(weights, prev, tcost) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(turnover, cost)`` [D] of :class:`BoxQPCost` for ``weights`` [D, N]."""
+    D, N = weights.shape
+    dev = weights.device
+    pv = torch.nan_to_num(_rows(prev, D, N, dev, "prev"), nan=0.0, posinf=0.0, neginf=0.0)
+    kap = _rows(tcost, D, N, dev, "tcost")
+    kap = torch.where(torch.isfinite(kap), kap, torch.zeros_like(kap))
+    trade = (weights - pv).abs()
+    return trade.sum(-1), (kap * trade).sum(-1)
+
+
 def new_projection(D: int, N: int, device) -> Projection:
     z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=device)   # noqa: E731
     return Projection(z(D, N), z(D, N), z(D), z(D, 3),
@@ -407,7 +468,8 @@ def new_projection(D: int, N: int, device) -> Projection:
 
 def box_qp(X, cap, ret, ind, stats, P, F, spec_vol, q=None, lower=0.0, upper=1.0, budget=1.0,
            universe=None, tol: float = 1e-10, max_passes: int = 32, check_every: int = 4, *,
-           torch_ops: bool = False, stream_rows: bool = False) -> BoxQP:
+           torch_ops: bool = False, stream_rows: bool = False, prev=None,
+           tcost=None) -> BoxQP | BoxQPCost:
     """Solve the box-constrained QP of the module docstring for every date.
 
     Panel arguments, ``F`` [D, K, K], ``spec_vol`` and ``universe`` as in
@@ -421,7 +483,15 @@ def box_qp(X, cap, ret, ind, stats, P, F, spec_vol, q=None, lower=0.0, upper=1.0
     and Q <= 16 (``ValueError`` before any launch).  ``torch_ops`` runs the dense torch
     transcription on the tensors' device (the CPU path; on the GPU only as a timing
     comparison); ``stream_rows`` forces the projection kernel's re-streaming variant.
+
+    ``prev`` / ``tcost`` (a scalar, [N] or [D, N] each; both or neither, ``ValueError``
+    otherwise) add the linear trading cost ``sum_n tcost_n |h_n - prev_n|`` to the objective
+    (:mod:`.tcost_qp`) and return a :class:`BoxQPCost`.  A non-finite ``prev`` is 0; ``tcost`` =
+    +inf means "do not trade this name" (it ends at ``clip(prev, lower, upper)``); a NaN or
+    negative ``tcost`` on a stock of the universe makes the date ``INVALID``.  Without them the
+    call is what it was.
     """
+    check_tcost(prev, tcost)
     D, Q, N = X.shape
     K = 1 + P + Q
     dev = X.device
@@ -431,10 +501,11 @@ def box_qp(X, cap, ret, ind, stats, P, F, spec_vol, q=None, lower=0.0, upper=1.0
     if D == 0:
         e = torch.empty(0, dtype=torch.float64, device=dev)
         ei = torch.empty(0, dtype=torch.int32, device=dev)
-        return BoxQP(torch.empty(0, N, dtype=torch.float64, device=dev), e, e.clone(), ei,
-                     ei.clone())
+        r = BoxQP(torch.empty(0, N, dtype=torch.float64, device=dev), e, e.clone(), ei,
+                  ei.clone())
+        return r if tcost is None else BoxQPCost(*r, e.clone(), e.clone())
     pb = make_problem(X, cap, ret, ind, stats, P, F, spec_vol, q, lower, upper, budget, universe,
-                      dense)
+                      dense, prev, tcost)
     st, pj = new_state(D, K, dev), new_projection(D, N, dev)
     for it in range(1, max_passes + 1):
         run_pass(pb, st, pj, tol, stream_rows=stream_rows)
@@ -444,7 +515,8 @@ def box_qp(X, cap, ret, ind, stats, P, F, spec_vol, q=None, lower=0.0, upper=1.0
     status = torch.where(st.status == RUNNING, MAX_PASSES, st.status).to(torch.int32)
     dead = status >= INFEASIBLE
     nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
-    return BoxQP(weights=torch.where(dead[:, None], nan, pj.h),
-                 gamma=torch.where(dead, nan, pj.gamma),
-                 variance=torch.where(dead, nan, st.ds[:, 2]),
-                 passes=st.passes, status=status)
+    r = BoxQP(weights=torch.where(dead[:, None], nan, pj.h),
+              gamma=torch.where(dead, nan, pj.gamma),
+              variance=torch.where(dead, nan, st.ds[:, 2]),
+              passes=st.passes, status=status)
+    return r if tcost is None else BoxQPCost(*r, *trade_stats(r.weights, prev, tcost))

@@ -88,6 +88,20 @@ class ExposureQP(NamedTuple):
     status: torch.Tensor
 
 
+class ExposureQPCost(NamedTuple):
+    """:func:`exposure_qp` with ``prev`` / ``tcost``: the fields of :class:`ExposureQP`, then
+    ``turnover`` and ``cost`` [D] as in :class:`.box_qp.BoxQPCost`."""
+    weights: torch.Tensor
+    gamma: torch.Tensor
+    eta: torch.Tensor
+    exposure_gap: torch.Tensor
+    variance: torch.Tensor
+    passes: torch.Tensor
+    status: torch.Tensor
+    turnover: torch.Tensor
+    cost: torch.Tensor
+
+
 class EqProblem(NamedTuple):
     """What :func:`eq_step` reads besides the trial: ``J`` / ``F`` [D, K, K], ``d`` [K] (1 on the
     nu slots, 0 on the mu slots), ``tau`` / ``DU`` [D, K], ``budget`` [D]; ``KT`` = number of nu
@@ -316,7 +330,8 @@ def make_eq_problem(pb: bq.Problem, F, sel: list[int], targets) -> tuple[bq.Prob
 
 def exposure_qp(X, cap, ret, ind, stats, P, F, spec_vol, factors, targets, q=None, lower=0.0,
                 upper=1.0, budget=1.0, universe=None, tol: float = 1e-10, max_passes: int = 128,
-                check_every: int = 4, *, torch_ops: bool = False) -> ExposureQP:
+                check_every: int = 4, *, torch_ops: bool = False, prev=None,
+                tcost=None) -> ExposureQP | ExposureQPCost:
     """Solve the QP of the module docstring for every date.
 
     Panel arguments, ``F``, ``spec_vol``, ``q`` / ``lower`` / ``upper`` / ``budget`` /
@@ -328,7 +343,10 @@ def exposure_qp(X, cap, ret, ind, stats, P, F, spec_vol, factors, targets, q=Non
     budget-feasible, with its ``exposure_gap`` (an unattainable target ends this way).  ``ValueError`` before any
     launch for index 0, duplicates, indices out of range and, on the GPU, K > 64 or Q > 16.
     ``torch_ops`` runs the dense torch transcription on the tensors' device (the CPU path; on
-    the GPU only as a timing comparison)."""
+    the GPU only as a timing comparison).  ``prev`` / ``tcost`` add linear trading costs as in
+    :func:`.box_qp.box_qp` and return an :class:`ExposureQPCost`; with the multipliers ``eta``
+    the sign convention of the module docstring holds with the cost's subgradient added."""
+    bq.check_tcost(prev, tcost)
     D, Q, N = X.shape
     K = 1 + P + Q
     dev = X.device
@@ -340,16 +358,18 @@ def exposure_qp(X, cap, ret, ind, stats, P, F, spec_vol, factors, targets, q=Non
     nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
     if m == 0:
         r = bq.box_qp(X, cap, ret, ind, stats, P, F, spec_vol, q, lower, upper, budget, universe,
-                      tol, max_passes, check_every, torch_ops=torch_ops)
+                      tol, max_passes, check_every, torch_ops=torch_ops, prev=prev, tcost=tcost)
         gap = torch.where(r.status >= INFEASIBLE, nan, torch.zeros_like(r.variance))
-        return ExposureQP(r.weights, r.gamma, r.variance.new_zeros(D, 0), gap, r.variance,
-                          r.passes, r.status)
+        e = ExposureQP(r.weights, r.gamma, r.variance.new_zeros(D, 0), gap, r.variance,
+                       r.passes, r.status)
+        return e if tcost is None else ExposureQPCost(*e, r.turnover, r.cost)
     if D == 0:
         e = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)   # noqa: E731
         ei = lambda: torch.empty(0, dtype=torch.int32, device=dev)        # noqa: E731
-        return ExposureQP(e(0, N), e(0), e(0, m), e(0), e(0), ei(), ei())
+        r = ExposureQP(e(0, N), e(0), e(0, m), e(0), e(0), ei(), ei())
+        return r if tcost is None else ExposureQPCost(*r, e(0), e(0))
     pb = bq.make_problem(X, cap, ret, ind, stats, P, F, spec_vol, q, lower, upper, budget,
-                         universe, dense)
+                         universe, dense, prev, tcost)
     pb, ep = make_eq_problem(pb, F, sel, targets)
     es = new_eq_state(D, K, dev)
     pjs = (bq.new_projection(D, N, dev), bq.new_projection(D, N, dev))
@@ -357,8 +377,8 @@ def exposure_qp(X, cap, ret, ind, stats, P, F, spec_vol, factors, targets, q=Non
     for it in range(1, max_passes + 1):
         # trial `it` goes into buffer it & 1, so that the trial before it survives it; gamma of
         # the running dates is carried over as the root find's warm start
-        pj, prev = pjs[it & 1], pjs[(it & 1) ^ 1]
-        pj.gamma.copy_(torch.where(st.status == RUNNING, prev.gamma, pj.gamma))
+        pj, last = pjs[it & 1], pjs[(it & 1) ^ 1]
+        pj.gamma.copy_(torch.where(st.status == RUNNING, last.gamma, pj.gamma))
         G, x = bq.run_trial(pb, st, pj)
         eq_step(G, ep, x, pj.stats, pj.flag, es, tol, parity=it & 1, torch_ops=dense)
         if check_every and it % check_every == 0 and it < max_passes \
@@ -370,9 +390,10 @@ def exposure_qp(X, cap, ret, ind, stats, P, F, spec_vol, factors, targets, q=Non
     odd = es.which == 1
     h = torch.where(odd[:, None], pjs[1].h, pjs[0].h)
     gam = torch.where(odd, pjs[1].gamma, pjs[0].gamma)
-    return ExposureQP(weights=torch.where(dead[:, None], nan, h),
-                      gamma=torch.where(dead, nan, gam),
-                      eta=torch.where((status != OK)[:, None], nan, es.eta[:, ep.KT:]),
-                      exposure_gap=torch.where(dead, nan, st.ds[:, 3]),
-                      variance=torch.where(dead, nan, st.ds[:, 2]),
-                      passes=st.passes, status=status)
+    r = ExposureQP(weights=torch.where(dead[:, None], nan, h),
+                   gamma=torch.where(dead, nan, gam),
+                   eta=torch.where((status != OK)[:, None], nan, es.eta[:, ep.KT:]),
+                   exposure_gap=torch.where(dead, nan, st.ds[:, 3]),
+                   variance=torch.where(dead, nan, st.ds[:, 2]),
+                   passes=st.passes, status=status)
+    return r if tcost is None else ExposureQPCost(*r, *bq.trade_stats(r.weights, prev, tcost))

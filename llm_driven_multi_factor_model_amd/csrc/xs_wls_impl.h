@@ -57,7 +57,7 @@ enum XsStatus : int {
   XS_NO_ROWS = 1,        // no valid stock on the date
   XS_PIVOT_EMPTY = 2,    // constraint pivot industry has zero capital
   XS_NEAR_SINGULAR = 4,  // Schur Cholesky lost > 12 digits: refined with the pseudo-inverse
-  XS_ZERO_PIVOT = 8,     // exactly-zero pivots / empty industries (pinv semantics -> f = 0)
+  XS_ZERO_PIVOT = 8,     // exactly-zero Schur pivots (set with NEAR_SINGULAR: refined too)
   XS_BAD_SIGMA = 16,     // pooled style std is zero / NaN
   XS_REFINED = 32,       // re-solved on the device with the eigen pseudo-inverse (pinv)
   XS_PINV_CUT = 128,     // that pinv dropped an eigen-direction below 1e-15 lambda_max (a
@@ -562,7 +562,8 @@ __device__ __forceinline__ void solve_body(double* sm, int d, int P, int Pseg, i
   const double nval = acc[NG + 2 * Q + 3];
   const double nq = nval * Q;
   const double mx = acc[NG + 2 * Q + 1] / nq;
-  const double sigma = sqrt(fmax(acc[NG + 2 * Q + 2] / nq - mx * mx, 0.0));
+  const double var = acc[NG + 2 * Q + 2] / nq - mx * mx;
+  const double sigma = sqrt(var < 0.0 ? 0.0 : var);  // a date without valid rows keeps its NaN
   const double isig = 1.0 / sigma;
   const double iSc = 1.0 / Sc;
   int st = 0;
@@ -707,8 +708,9 @@ __device__ __forceinline__ void solve_body(double* sm, int d, int P, int Pseg, i
 #pragma unroll
   for (int k = 0; k < ND; ++k) {
     const double dk = Lm[k * (k + 1) / 2 + k];
-    if (!(dk > ztol)) {  // pinv semantics: drop the direction (exactly singular block)
-      st |= (dorig[k] > ztol) ? XS_NEAR_SINGULAR : XS_ZERO_PIVOT;
+    if (!(dk > ztol)) {  // drop the direction; the pinv pass re-solves the date: a column inside
+      // the industries' span (zero Schur diagonal) is not a zero column, pinv gives it a share
+      st |= (dorig[k] > ztol) ? XS_NEAR_SINGULAR : XS_NEAR_SINGULAR | XS_ZERO_PIVOT;
       il[k] = 0.0;
 #pragma unroll
       for (int i = k; i < ND; ++i) Lm[i * (i + 1) / 2 + k] = 0.0;
@@ -762,8 +764,8 @@ __device__ __forceinline__ void solve_body(double* sm, int d, int P, int Pseg, i
   for (int k = 0; k < ND; ++k) {
     const double dk = readlane(Li[k], k);
     const double dok = readlane(dori, k);
-    if (!(dk > ztol)) {  // pinv semantics: drop the direction (exactly singular block)
-      st |= (dok > ztol) ? XS_NEAR_SINGULAR : XS_ZERO_PIVOT;
+    if (!(dk > ztol)) {  // drop the direction; the pinv pass re-solves the date (see above)
+      st |= (dok > ztol) ? XS_NEAR_SINGULAR : XS_NEAR_SINGULAR | XS_ZERO_PIVOT;
       il[k] = 0.0;
       if (lane >= k) Li[k] = 0.0;
       continue;

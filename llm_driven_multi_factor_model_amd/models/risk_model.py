@@ -656,6 +656,37 @@ class RiskModel:
         return Portfolio(r.weights, r.variance, r.passes, r.status, active, ret, gap, eta,
                          *((r.turnover, r.cost) if tc else ()))
 
+    def risk_budget(self, budgets=None, budget=1.0, which: str = "vra",
+                    specific_vol: torch.Tensor | str = "shrunk",
+                    universe: torch.Tensor | None = None,
+                    dates: tuple[int, int] | None = None, **solver):
+        """Risk-budgeting (risk-parity) portfolio of every date
+        (:func:`ops.risk_budget.risk_budget`): the long-only, fully invested ``h`` with
+        ``h_n (Sigma h)_n / h^T Sigma h = b_n / sum b`` on the stocks with a budget ``b_n > 0``.
+        ``budgets``: None (equal risk contribution), [N] or [D_loc, N]; ``budget`` (the sum of
+        the weights) a scalar or [D_loc]; ``which`` / ``specific_vol`` / ``universe`` /
+        ``dates`` as in :meth:`optimize`; ``solver`` passes ``tol``, ``max_passes``,
+        ``check_every`` and ``theta`` on.  Returns :class:`ops.risk_budget.RiskBudget`; dates
+        with an empty universe or an invalid covariance give NaN rows (see ``status``).  Per
+        date: the only collective is the one ``"shrunk"`` makes."""
+        from ..ops import risk_budget as rbm
+        cov, sv = self._cov_inputs(which, specific_vol)
+        p, stats = self.panel, self.stats
+        if dates is not None:
+            a0, b0 = dates
+            D_all = p.D
+            p, stats, cov = p.slice_dates(a0, b0), stats[a0:b0], cov[a0:b0]
+
+            def cut(t, per_date_dim=2):
+                if isinstance(t, torch.Tensor) and t.dim() >= per_date_dim \
+                        and t.shape[0] == D_all:
+                    return t[a0:b0]
+                return t
+            sv, budgets, universe = map(cut, (sv, budgets, universe))
+            budget = cut(budget, 1)
+        return rbm.risk_budget(p.styles, p.cap, p.ret, p.ind, stats, p.P, cov, sv, budgets,
+                               budget, universe, **solver)
+
     def rebalance(self, start: torch.Tensor | None = None, drift: bool = True,
                   **optimize_kwargs) -> Portfolio:
         """A path of holdings over the local dates: date t is solved by :meth:`optimize`

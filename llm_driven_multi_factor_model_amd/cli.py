@@ -5,7 +5,8 @@
         --industry data/industry_info.csv --out results/ [--preset reference] [--sims 100] \
         [--checkpoint risk.ckpt] [--resume risk.ckpt] [--attribution equal] [--mongo-uri URI] \
         [--specific-model use4] [--time-scan carry] [--no-deterministic] [--bias-stat 21 --bias-start 1000] \
-        [--bias-test portfolios.csv] [--factor-stats] [--factor-ic --ic-horizons 1,5,20 --ic-quantiles 5]
+        [--bias-test portfolios.csv] [--factor-stats] [--factor-ic --ic-horizons 1,5,20 --ic-quantiles 5] \
+        [--asset-cov names.csv --asset-cov-date 2020-01-02 --asset-cov-correlation]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m llm_driven_multi_factor_model_amd.cli risk ...
     python -m llm_driven_multi_factor_model_amd.cli factors --prices prices.csv --index index.csv \
         --industry sw_industry.csv --out data/
@@ -121,6 +122,9 @@ def cmd_risk(a):
     if a.bias_test:
         paths["bias_test"] = _write_bias_test(model, a.bias_test, a.out, ctx, a.specific_model,
                                               a.bias_test_window)
+    if a.asset_cov:
+        paths["asset_cov"] = _write_asset_cov(model, a.asset_cov, a.out, ctx, a.specific_model,
+                                              a.asset_cov_date, a.asset_cov_correlation)
     if a.factor_stats:
         paths.update(_write_factor_stats(model, a.out, ctx))
     if a.factor_ic:
@@ -200,6 +204,35 @@ def _write_bias_test(model, spec: str, out_dir: str, ctx, specific_model: str = 
                            "mrad": colmean((got["rb"] - 1.0).abs()),
                            "coverage": colmean(got["cov"])},
                           index=pd.Index(names, name="portfolio"))
+        os.makedirs(out_dir, exist_ok=True)
+        df.to_csv(path)
+    return path
+
+
+def _write_asset_cov(model, spec: str, out_dir: str, ctx, specific_model: str = "trailing",
+                     date: str | None = None, correlation: bool = False):
+    """Asset covariance (``correlation``: correlation) block of the names in the CSV ``spec``
+    (column ``stocknames``) on one date, default the last (``RiskModel.asset_cov``, VRA
+    covariance).  Collective; rank 0 writes ``asset_cov.csv``, an M x M matrix labelled by name
+    (NaN rows and columns for names outside that date's universe)."""
+    from .parallel import dist as pdist
+    names = [str(s) for s in pd.read_csv(spec)["stocknames"]]
+    dates = pd.DatetimeIndex(model._global_dates())
+    target = dates[-1] if date is None else pd.Timestamp(date)
+    if target not in dates:
+        raise SystemExit(f"--asset-cov-date {date}: not a date of the panel")
+    local = np.nonzero(pd.DatetimeIndex(model.panel.dates) == target)[0]
+    t = (int(local[0]), int(local[0]) + 1) if len(local) else (0, 0)   # the owner's one row
+    try:
+        r = model.asset_cov(names, specific_vol="use4" if specific_model == "use4" else "shrunk",
+                            dates=t, correlation=correlation)
+    except KeyError as e:
+        raise SystemExit(f"--asset-cov {spec}: {e.args[0]}")
+    got = pdist.gather_to_root(r.cov.contiguous(), ctx)
+    path = os.path.join(out_dir, "asset_cov.csv")
+    if ctx.rank == 0:
+        df = pd.DataFrame(got[0].cpu().numpy(), index=pd.Index(names, name="stocknames"),
+                          columns=names)
         os.makedirs(out_dir, exist_ok=True)
         df.to_csv(path)
     return path
@@ -430,6 +463,13 @@ def main(argv=None):
                         "--specific-model)")
     r.add_argument("--bias-test-window", type=int, default=252,
                    help="window of the rolling bias statistic behind bias_test.csv")
+    r.add_argument("--asset-cov", default=None,
+                   help="a CSV (stocknames): write asset_cov.csv, the labelled asset covariance "
+                        "matrix of those names on one date (honours --specific-model)")
+    r.add_argument("--asset-cov-date", default=None, metavar="YYYY-MM-DD",
+                   help="date of asset_cov.csv (default: the last date)")
+    r.add_argument("--asset-cov-correlation", action="store_true",
+                   help="write correlations instead of covariances to asset_cov.csv")
     r.add_argument("--factor-stats", action="store_true",
                    help="write factor_tstats.csv (date, factor, f, se, t) and "
                         "factor_significance.csv (per factor: mean |t|, share of dates with "

@@ -687,6 +687,43 @@ class RiskModel:
         return rbm.risk_budget(p.styles, p.cap, p.ret, p.ind, stats, p.P, cov, sv, budgets,
                                budget, universe, **solver)
 
+    def asset_cov(self, stocks, which: str = "vra", specific_vol: torch.Tensor | str = "shrunk",
+                  universe: torch.Tensor | None = None,
+                  dates: tuple[int, int] | None = None, correlation: bool = False):
+        """Dense asset covariance (``correlation``: correlation) block ``Sigma_d[S, S]`` of a
+        basket on every local date (:func:`ops.asset_cov.asset_cov`).  ``stocks``: a list of
+        names of ``panel.stocks`` (``KeyError`` names an unknown one), or an index tensor [M]
+        (the same basket every date) / [D_loc, M] (a basket per date, -1 = padding).  ``which``
+        / ``specific_vol`` / ``universe`` / ``dates`` as in :meth:`optimize`.  Returns
+        :class:`ops.asset_cov.AssetCov`: ``cov`` [D, M, M], ``vol`` / ``valid`` [D, M]; members
+        outside the universe give NaN rows and columns.  Per date: the only collective is the
+        one ``"shrunk"`` makes."""
+        from ..ops import asset_cov as ac
+        cov, sv = self._cov_inputs(which, specific_vol)
+        p, stats = self.panel, self.stats
+        if isinstance(stocks, torch.Tensor):
+            index = stocks
+        else:
+            pos = {str(s): i for i, s in enumerate(p.stocks)}
+            missing = [str(s) for s in stocks if str(s) not in pos]
+            if missing:
+                raise KeyError(f"unknown stock name(s): {', '.join(missing)}")
+            index = torch.tensor([pos[str(s)] for s in stocks], dtype=torch.int64)
+        if index.dim() == 2 and index.shape[0] != p.D:
+            raise ValueError(f"a per-date index must have {p.D} rows, got {index.shape[0]}")
+        if dates is not None:
+            a0, b0 = dates
+            D_all = p.D
+            p, stats, cov = p.slice_dates(a0, b0), stats[a0:b0], cov[a0:b0]
+
+            def cut(t):
+                if isinstance(t, torch.Tensor) and t.dim() >= 2 and t.shape[0] == D_all:
+                    return t[a0:b0]
+                return t
+            sv, universe, index = map(cut, (sv, universe, index))
+        return ac.asset_cov(p.styles, p.cap, p.ret, p.ind, stats, p.P, cov, sv,
+                            index.to(self.device), universe, correlation)
+
     def rebalance(self, start: torch.Tensor | None = None, drift: bool = True,
                   **optimize_kwargs) -> Portfolio:
         """A path of holdings over the local dates: date t is solved by :meth:`optimize`

@@ -16,6 +16,7 @@ its exposures exist on that date (finite styles and capital, a known industry). 
 return is not required, unlike the regression universe.
 """
 import logging
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -23,6 +24,14 @@ import torch
 from .ops import attribution as attr
 
 log = logging.getLogger("mfa.serving")
+
+
+class ServiceCov(NamedTuple):
+    """:meth:`RiskService.covariance`: ``cov`` [M, M] float64 over the ``kept`` names (in the
+    order asked for), and the names that were ``ignored`` (unknown, or without exposures)."""
+    cov: torch.Tensor
+    kept: list
+    ignored: list
 
 
 class RiskService:
@@ -95,6 +104,32 @@ class RiskService:
         svar = (H * H) @ self.s2                                        # [B]
         return attr.risk_attribution(x, self.F.expand(H.shape[0], -1, -1), svar)
 
+    def covariance(self, names, correlation: bool = False) -> ServiceCov:
+        """Asset covariance (``correlation``: correlation) block of ``names`` on the snapshot
+        date, ``X_S F X_S^T + s^2`` where two entries name the same stock: one small GEMM from
+        the service's own ``X``, ``F`` and ``s2``.  Membership is ``held_ok``, as in
+        :meth:`query`; the lower triangle is mirrored, so the block is symmetric bit for bit."""
+        ok = self.held_ok.cpu().numpy()
+        kept, ignored, pos = [], [], []
+        for name in map(str, names):
+            i = self._pos.get(name)
+            if i is None or not ok[i]:
+                ignored.append(name)
+            else:
+                kept.append(name)
+                pos.append(i)
+        idx = torch.tensor(pos, dtype=torch.long, device=self.device)
+        Xs = self.X[idx]                                                # [M, K]
+        low = torch.tril((Xs @ self.F) @ Xs.T)
+        cov = low + torch.tril(low, -1).T
+        zero = torch.zeros((), dtype=torch.float64, device=self.device)
+        cov = cov + torch.where(idx[:, None] == idx[None, :], self.s2[idx][:, None], zero)
+        if correlation:
+            vol = torch.sqrt(torch.diagonal(cov))
+            cov = cov / (vol[:, None] * vol[None, :])
+            torch.diagonal(cov).fill_(1.0)
+        return ServiceCov(cov, kept, ignored)
+
     def query_json(self, portfolios: list[dict]) -> list[dict]:
         H, unknown = self.weights(portfolios)
         r = self.query(H)
@@ -122,7 +157,9 @@ class RiskService:
 
 def make_app(service: RiskService):
     """FastAPI app: ``GET /health``, ``GET /factors``, ``POST /risk`` with
-    ``{"portfolios": [{"000001.SZ": 0.5, ...}, ...]}`` (or a single ``{"weights": {...}}``)."""
+    ``{"portfolios": [{"000001.SZ": 0.5, ...}, ...]}`` (or a single ``{"weights": {...}}``), and
+    ``POST /cov`` with ``{"stocks": [...], "correlation": false}``, which answers
+    ``{"date", "stocks", "ignored", "cov"}`` (the block over the stocks that were kept)."""
     # (no `from __future__ import annotations` in this module: FastAPI resolves the request
     # model from the live annotation of the nested route function)
     from fastapi import FastAPI, HTTPException
@@ -131,6 +168,10 @@ def make_app(service: RiskService):
     class RiskRequest(BaseModel):
         portfolios: list[dict[str, float]] | None = None
         weights: dict[str, float] | None = None
+
+    class CovRequest(BaseModel):
+        stocks: list[str]
+        correlation: bool = False
 
     app = FastAPI(title="MI355X Barra risk service")
 
@@ -150,5 +191,14 @@ def make_app(service: RiskService):
         if len(pfs) > 65536:
             raise HTTPException(status_code=413, detail="at most 65536 portfolios per request")
         return {"results": service.query_json(pfs)}
+
+    @app.post("/cov")
+    def cov(req: CovRequest):
+        if len(req.stocks) > 4096:
+            raise HTTPException(status_code=413, detail="at most 4096 stocks per request")
+        r = service.covariance(req.stocks, req.correlation)
+        # a non-finite entry (a non-finite F on the snapshot date) is null in JSON
+        rows = [[v if np.isfinite(v) else None for v in row] for row in r.cov.cpu().tolist()]
+        return {"date": service.date, "stocks": r.kept, "ignored": r.ignored, "cov": rows}
 
     return app
